@@ -7,11 +7,11 @@ N > 1: one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set) this proc
 the N ranks itself as child processes BEFORE anything touches the GPU (launch_ranks) and exits with their status.  Either
 way the process group's world size must equal --gpus.
 
-A step is one full MSM (kg_msm: scalars + bases resident in HBM -> one projective point on the host).  The headline is the
-MEDIAN of --rounds (5) timed rounds of K steps each, every round bracketed by a barrier + device synchronisation, max over
-ranks (`rounds_ms` lists them).  With N > 1 the index range of an N * 2^20 commitment is sharded: every rank runs the same
-pipeline on its own 2^20 slice and the per-rank affine partial sums (9 words) are all-gathered over RCCL and added (weak
-scaling).
+A step is one full MSM (kg_msm: scalars + bases resident in HBM -> one projective point on the host).  Exactly K steps are
+timed, split into --rounds (1) rounds, every round bracketed by a barrier + device synchronisation, max over ranks (`rounds_ms`
+lists them); `ms_per_step` is the time of all K steps over K.  --dump-outputs DIR writes the point of the last timed step.
+With N > 1 the index range of an N * 2^20 commitment is sharded: every rank runs the same pipeline on its own 2^20 slice and
+the per-rank affine partial sums (9 words) are all-gathered over RCCL and added (weak scaling).
 
 Rank 0 prints ONE JSON line.  Its first key is `summary`: every leg's headline figure, flat.  The legs: `roofline` /
 `valu_roofline` / `cpu_baseline` of the headline, `blocking_ms`, `msm_host_scalars`, `msm_strong`, `msm_skewed`, `msm_g2`
@@ -31,9 +31,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The library's queues (main, scalar, two reduction queues) want a hardware queue each; the runtime reads this when HIP
-# initialises, which torch does before the library is loaded (csrc/capi.cpp sets the same default for hosts that load it first).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 SEED = 0x4B6F676172617368
 LOG_N = 20
@@ -61,6 +58,18 @@ def point_digest(xy, inf):
     import hashlib
     import numpy as np
     return "identity" if inf else hashlib.sha256(np.ascontiguousarray(xy, dtype=np.uint64).tobytes()).hexdigest()[:16]
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs: what the last timed step returned, the affine point (xy, inf) of the G1 MSM (combined over the ranks), exactly
+    in float64: g1_msm_xy.npy = (2, 8) x and y as the 32-bit little-endian words of their Montgomery limbs (R = 2^256),
+    g1_msm_inf.npy = (1,) 1.0 for the identity.  The inputs come from fixed seeds, so equal arguments give equal files."""
+    import numpy as np
+    xy, inf = res
+    os.makedirs(dirname, exist_ok=True)
+    words = np.ascontiguousarray(xy, dtype="<u8").view("<u4").reshape(2, 8)
+    np.save(os.path.join(dirname, "g1_msm_xy.npy"), words.astype(np.float64))
+    np.save(os.path.join(dirname, "g1_msm_inf.npy"), np.array([float(inf)], dtype=np.float64))
 
 
 def r3(x):
@@ -99,19 +108,24 @@ def single_rank_env(torch, dev):
             "kdist": None}
 
 
-def timed_rounds(env, fn, steps, rounds):
-    """`rounds` timed rounds of fn(steps), each bracketed by the rank barrier + device synchronisation, max over ranks per round;
-    returns (median seconds per round, [ms per step of every round], the last result)"""
+def time_rounds(env, fn, sizes):
+    """one timed round of fn(k) per k in `sizes`, each bracketed by the rank barrier + device synchronisation, max over ranks per
+    round; returns ([seconds of every round], the last result)"""
     out, res = [], None
     gc.collect()
-    for _ in range(rounds):
+    for k in sizes:
         env["barrier"]()
         t0 = time.perf_counter()
-        res = fn(steps)
+        res = fn(k)
         env["barrier"]()
         out.append(env["max_over_ranks"](time.perf_counter() - t0))
-    med = sorted(out)[len(out) // 2]
-    return med, [round(x / steps * 1e3, 4) for x in out], res
+    return out, res
+
+
+def timed_rounds(env, fn, steps, rounds):
+    """`rounds` timed rounds of fn(steps); returns (median seconds per round, [ms per step of every round], the last result)"""
+    out, res = time_rounds(env, fn, [steps] * rounds)
+    return sorted(out)[len(out) // 2], [round(x / steps * 1e3, 4) for x in out], res
 
 
 def bench_msm_strong(ctx, torch, dev, K, env, log_n, steps):
@@ -208,7 +222,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=5, help="timed rounds of --steps steps each; the headline is the median round")
+    ap.add_argument("--rounds", type=int, default=None,
+                    help="rounds the --steps timed steps of the headline are split into (default 1; rounds_ms lists each round); "
+                         "with --msm-g2-only: timed rounds of --steps steps each, the median one reported (default 5)")
     ap.add_argument("--log-n", type=int, default=LOG_N)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ntt", action="store_true")
@@ -231,14 +247,23 @@ def main():
     ap.add_argument("--depth", type=int, default=4, help="MSM steps in flight (1..4)")
     ap.add_argument("--prewarm", type=int, default=200, help="untimed steps before the W warm-up steps (first touch, clock ramp)")
     ap.add_argument("--stream-ordered-inputs", action="store_true", help="do not declare the (static, synchronised) inputs complete")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the point the last timed step computed to DIR/*.npy (float64)")
     args = ap.parse_args()
     # like timeit: no cyclic garbage collection inside timed loops (a generation-2 pass is a 30-40 ms pause that lands in whichever call
     # happens to allocate the object that triggers it -- tools/dbg/anom_1024.py); every leg collects before it starts its clock
     gc.disable()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
-    if args.rounds < 1:
-        ap.error("--rounds must be >= 1")
+    if args.msm_g2_only:
+        args.rounds = 5 if args.rounds is None else args.rounds
+        if args.rounds < 1:
+            ap.error("--rounds must be >= 1")
+    else:
+        args.rounds = 1 if args.rounds is None else args.rounds
+        if args.steps < 1 or not 1 <= args.rounds <= args.steps:
+            ap.error("--steps must be >= 1 and --rounds between 1 and --steps")
+    if args.dump_outputs and (args.ntt_only or args.msm_g2_only or args.groth16_only or args.small_only):
+        ap.error("--dump-outputs writes the headline MSM's result; the --*-only modes do not run it")
     NOTES = args.notes
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -363,9 +388,12 @@ def main():
     if args.warmup:
         run(args.warmup)
     ctx.profile_enable(True)
-    # the timed region: --rounds rounds of EXACTLY --steps steps, each bracketed by barrier + synchronisation; the median round is the
-    # headline (a 27 ms window moves 2-4 % between runs on a box whose host cores are shared)
-    elapsed, rounds_ms, res = timed_rounds(env, run, args.steps, args.rounds)
+    # the timed region: EXACTLY --steps steps, split into --rounds rounds (one by default), each bracketed by barrier + synchronisation;
+    # ms_per_step is the time of all of them over --steps
+    sizes = [args.steps // args.rounds + (r_ < args.steps % args.rounds) for r_ in range(args.rounds)]
+    secs, res = time_rounds(env, run, sizes)
+    elapsed = sum(secs)
+    rounds_ms = [round(t_ / k_ * 1e3, 4) for t_, k_ in zip(secs, sizes)]
     summary = ctx.profile_summary()           # HIP events recorded on the launch streams during ALL timed rounds
     ctx.profile_enable(False)
     acc_avg_ms = summary["accumulate"][0] / summary["accumulate"][1]
@@ -396,6 +424,8 @@ def main():
     }
     if NOTES:
         line["phases_ms_per_step"] = phase_avg
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     if args.headline_only:
         if rank == 0:
             print(json.dumps(compact({"summary": {"msm_ms_per_step": r3(line["ms_per_step"]), "msm_pairs_per_s": value, "acc_kernel_ms": r3(acc_avg_ms)}, **line})), flush=True)

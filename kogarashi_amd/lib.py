@@ -87,9 +87,8 @@ def load():
 
 
 def init() -> bool:
-    """kg_init: one hardware queue per library queue (GPU_MAX_HW_QUEUES=16 unless set).  Explicit and optional: call it
-    before anything initialises HIP (importing torch does not; the first torch.cuda call or Context does).  The package
-    never changes the environment by itself."""
+    """kg_init: kept for the ABI, sets nothing (False).  The hardware queue count (GPU_MAX_HW_QUEUES) is the machine's
+    setting; the package never changes the environment."""
     return bool(load().kg_init())
 
 

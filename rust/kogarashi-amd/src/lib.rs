@@ -181,9 +181,7 @@ mod global {
         let mut guard = CTXS.lock().ok()?;
         if guard.is_none() {
             let mut v = Vec::new();
-            // one hardware queue per library queue; a no-op when the host exported GPU_MAX_HW_QUEUES or initialised HIP itself.
-            // The glue's first backend call is the host's opt-in (`gpu` feature): call `kogarashi_amd::contexts()` from the
-            // single-threaded start-up path if other threads may be reading the environment later (kg_init calls setenv).
+            // kept for the ABI: kg_init sets nothing (the hardware queue count is the machine's setting).
             unsafe { sys::kg_init() };
             let n = Context::device_count();
             for d in 0..n.max(0) {

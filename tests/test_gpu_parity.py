@@ -739,12 +739,15 @@ def test_skewed_scalar_vectors_over_the_three_curves():
 
 
 def test_service_queues_are_placed_off_the_main_queues_pipe(ctx):
-    """capi.cpp place_queues: in a fresh process (none but the runtime's own streams, GPU_MAX_HW_QUEUES as the suite sets it) the probe
-    finds exactly the candidates j and j + 4 on the main queue's compute pipe (2 <= code <= 5), also with never-used streams created
-    first; in THIS process -- hundreds of streams and contexts behind it -- any answer is a status-clean code 0..5 (1 = no clear
-    picture: creation order, which only costs speed)."""
+    """capi.cpp place_queues: in a fresh process (none but the runtime's own streams) with at least four hardware queues (the
+    machine's GPU_MAX_HW_QUEUES; the runtime's default is 4) the probe finds exactly the candidates j and j + 4 on the main queue's
+    compute pipe (2 <= code <= 5), also with never-used streams created first; with fewer, every candidate shares a queue with the main
+    queue or alternates with it, there is no such picture to find and every process must say so (1); in THIS process -- hundreds of
+    streams and contexts behind it -- any answer is a status-clean code 0..5 (1 = no clear picture: creation order, which only costs speed)."""
     import os, subprocess, sys
+    from kogarashi_amd.lib import hw_queue_setting
     assert 0 <= ctx.queue_placement() <= 5
+    pipes_seen = (hw_queue_setting() or 4) >= 4
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = "import sys; sys.path.insert(0, %r)\nimport kogarashi_amd as K\nc = K.Context(0); print('placement', c.queue_placement()); c.close()" % root
     for env in ({}, {"KG_STREAM_PAD": "1,2"}):
@@ -756,6 +759,9 @@ def test_service_queues_are_placed_off_the_main_queues_pipe(ctx):
             seen.append(int(r.stdout.split("placement")[1].split()[0]))
             if 2 <= seen[-1] <= 5:
                 break
-        assert 2 <= seen[-1] <= 5 and all(v == 1 for v in seen[:-1]), (env, seen)
+        if pipes_seen:
+            assert 2 <= seen[-1] <= 5 and all(v == 1 for v in seen[:-1]), (env, seen)
+        else:
+            assert seen == [1, 1, 1], (env, seen, hw_queue_setting())
     r = subprocess.run([sys.executable, "-c", script], env=dict(os.environ, KG_QUEUE_PLACEMENT="0"), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and int(r.stdout.split("placement")[1].split()[0]) == 0
