@@ -1,9 +1,12 @@
 """Builds libkogarashi_amd.so (HIP kernels + C ABI) for gfx950, in-tree.
 
-    python -m kogarashi_amd.build [--force] [--jobs N] [--experiments]
+    python -m kogarashi_amd.build [--force] [--jobs N] [--experiments] [--devprobe]
 
 --experiments builds libkogarashi_amd_exp.so beside the product library: the same sources with -DKG_EXPERIMENTS, i.e. plus the three
 kernels that lost their A/B runs (kg_experiments_built() == 1; loaded through KG_LIB_PATH by their parity tests and by A/B scripts).
+
+--devprobe builds tests/device/libdevprobe.so: test-only kernels that run the csrc/ templates one primitive at a time (tests/test_gpu_primitives.py),
+compiled with the same FLAGS as the product so that they run the code the product's kernels run.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container; the resulting .so is
 git-ignored but travels to the GPU box with the repo snapshot."""
@@ -57,10 +60,35 @@ def build(force: bool = False, jobs: int = 4, experiments: bool = False) -> str:
     return out
 
 
+DEVPROBE_DIR = os.path.join(os.path.dirname(HERE), "tests", "device")
+DEVPROBE_SRC = os.path.join(DEVPROBE_DIR, "devprobe.hip")
+DEVPROBE_OUT = os.path.join(DEVPROBE_DIR, "libdevprobe.so")
+
+
+def devprobe_deps() -> list[str]:
+    """what libdevprobe.so is made from: its source, the shared cases and every header under csrc/"""
+    headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith((".h", ".inc"))]
+    return [DEVPROBE_SRC, os.path.join(os.path.dirname(DEVPROBE_DIR), "host", "arith_cases.h")] + headers
+
+
+def build_devprobe(force: bool = False) -> str:
+    if force or _stale(DEVPROBE_OUT, devprobe_deps()):
+        tmp = DEVPROBE_OUT + f".{os.getpid()}.tmp"      # (no object file: one source; renamed into place so that a reader never sees half a file)
+        cmd = ["hipcc", "-x", "hip"] + FLAGS + ["-shared", DEVPROBE_SRC, "-o", tmp]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise RuntimeError(f"hipcc failed for devprobe.hip:\n{r.stderr[-6000:]}")
+        os.replace(tmp, DEVPROBE_OUT)
+    return DEVPROBE_OUT
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--jobs", type=int, default=4)
     ap.add_argument("--experiments", action="store_true")
+    ap.add_argument("--devprobe", action="store_true")
     a = ap.parse_args()
-    print(build(a.force, a.jobs, a.experiments))
+    print(build_devprobe(a.force) if a.devprobe else build(a.force, a.jobs, a.experiments))

@@ -115,12 +115,17 @@ __global__ void __launch_bounds__(64) k_probe_nop(uint32_t* p) { if (p) *p = 1; 
 
 static int place_queues(kg_ctx* c) {
   if (c->queues_placed) return KG_OK;
-  constexpr int NC = 8;
-  hipStream_t cand[NC] = {};
+  // The first streams a process launches on are not dealt like the later ones (measured in a process with four hardware queues: of twelve
+  // streams created and first used in order behind the main queue, numbers 6 and 10 share its pipe and number 2 does not -- the probe then
+  // never saw "j and j + 4" among eight candidates), so LEAD streams are created and launched on in front of the eight candidates; they
+  // take part in the probe and are released after it (tests/test_gpu_parity.py test_service_queues_are_placed_off_the_main_queues_pipe).
+  constexpr int LEAD = 4, NC = 8;
+  hipStream_t all[LEAD + NC] = {};
+  hipStream_t* const cand = all + LEAD;
   hipError_t e = hipSuccess;
-  for (int j = 0; j < NC && e == hipSuccess; ++j) e = create_stream(c, &cand[j], true);
+  for (int j = 0; j < LEAD + NC && e == hipSuccess; ++j) e = create_stream(c, &all[j], true);
   if (e != hipSuccess) {                                // nothing is kept: the candidates made so far are released, a later call tries again
-    for (int j = 0; j < NC; ++j) if (cand[j]) hipStreamDestroy(cand[j]);
+    for (int j = 0; j < LEAD + NC; ++j) if (all[j]) hipStreamDestroy(all[j]);
     return set_err(c, KG_ERR_HIP, "queue creation", e);
   }
   int cls[NC];
@@ -140,13 +145,17 @@ static int place_queues(kg_ctx* c) {
       ok = hipEventRecord(ev_s, c->stream) == hipSuccess;
       hipLaunchKernelGGL(k_probe_busy, dim3(6144), dim3(64), 64 * 1024, c->stream, 1000ull);      // 12 rounds of 512 resident workgroups x 10 us
       ok = ok && hipEventRecord(ev_a, c->stream) == hipSuccess;
+      for (int j = 0; j < LEAD && ok; ++j) {
+        ok = hipStreamWaitEvent(all[j], ev_s, 0) == hipSuccess;
+        hipLaunchKernelGGL(k_probe_nop, dim3(1), dim3(64), 0, all[j], (uint32_t*)nullptr);
+      }
       for (int j = 0; j < NC && ok; ++j) {
         ok = hipStreamWaitEvent(cand[j], ev_s, 0) == hipSuccess;
         hipLaunchKernelGGL(k_probe_nop, dim3(1), dim3(64), 0, cand[j], (uint32_t*)nullptr);
         ok = ok && hipEventRecord(ev_b[j], cand[j]) == hipSuccess;
       }
       ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
-      for (int j = 0; j < NC && ok; ++j) ok = hipStreamSynchronize(cand[j]) == hipSuccess;
+      for (int j = 0; j < LEAD + NC && ok; ++j) ok = hipStreamSynchronize(all[j]) == hipSuccess;
       float ta = 0.f;
       ok = ok && hipEventElapsedTime(&ta, ev_s, ev_a) == hipSuccess;
       for (int j = 0; j < NC && ok; ++j) {
@@ -178,7 +187,7 @@ static int place_queues(kg_ctx* c) {
   c->side2_stream = take(3);
   c->acc_stream[1] = take(0);
   c->up_stream = take(3);                                 // kg_msm_host's upload queue: copies only
-  for (int j = 0; j < NC; ++j) if (cand[j]) hipStreamDestroy(cand[j]);
+  for (int j = 0; j < LEAD + NC; ++j) if (all[j]) hipStreamDestroy(all[j]);      // the lead streams and the candidates nobody took
   c->queues_placed = true;                                // only now: every queue the context uses exists
   return KG_OK;
 }

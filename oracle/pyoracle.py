@@ -12,7 +12,7 @@ checked against an implementation that shares no code and no algorithm with them
 PARITY PINNING.  The reference (KogarashiNetwork/Kogarashi, Rust) cannot be built here (no
 rustc/cargo, un-vendored crates) and holds NO known-answer vectors for Montgomery multiplication,
 point addition, MSM, NTT or Groth16.  What it does hold are constants, and those are
-pinned in ``tests/test_oracle_constants.py``:
+pinned in ``tests/test_oracle_pinning.py``:
   bn254/src/fr.rs:10-65 (MODULUS, R, R2, R3, INV, S, ROOT_OF_UNITY, GENERATOR=7),
   bn254/src/fq.rs:9-42 (MODULUS, R, R2, R3, INV), bn254/src/params.rs:8-57 (G1/G2 generators, b),
   grumpkin/src/params.rs:4-19 (generator, b = -17).

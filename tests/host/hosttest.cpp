@@ -11,15 +11,12 @@
 #include "../../kogarashi_amd/csrc/msm_digits.h"
 #include "../../kogarashi_amd/csrc/coop_add.h"
 #include "../../kogarashi_amd/csrc/host_fp.h"
+#include "arith_cases.h"
 
 using namespace kg;
 
-template <class F> struct Conv;   // reference-form words <-> field type (plain or checked)
-template <class P> struct Conv<Fp<P>> {
-  static Fp<P> in(const uint32_t* w) { return from_ref<P>(w); }
-  static void out(const Fp<P>& a, uint32_t* w) { to_ref(a, w); }
-  static constexpr int W = 8;
-};
+// the checked type's side of arith_cases.h: ABI-form words and raw limbs enter it with the bounds their source vouches for
+namespace kgcase {
 template <class P> struct Conv<FpChecked<P>> {
   static FpChecked<P> in(const uint32_t* w) {
     FpChecked<P> raw = FpChecked<P>::wrap(limbs_from_words<P>(w), 5.4);   // any 256-bit input
@@ -30,34 +27,43 @@ template <class P> struct Conv<FpChecked<P>> {
   }
   static constexpr int W = 8;
 };
-template <class F> struct Conv<Fp2<F>> {
-  static Fp2<F> in(const uint32_t* w) { return {Conv<F>::in(w), Conv<F>::in(w + 8)}; }
-  static void out(const Fp2<F>& a, uint32_t* w) { Conv<F>::out(a.c0, w); Conv<F>::out(a.c1, w + 8); }
-  static constexpr int W = 16;
+// raw limbs of an operand class that declares {limb bound, top-limb bound, K}: wrap(limbs, K), the limb bounds widened to the class's where it
+// holds lazy limbs (0: normalised, as wrap assumes) -- and the actual limbs checked against them at once
+template <class P> struct Raw<FpChecked<P>> {
+  static FpChecked<P> limbs(const uint32_t* l, const double* bnd) {
+    FpChecked<P> r = FpChecked<P>::wrap(Raw<Fp<P>>::limbs(l, nullptr), bnd[2]);
+    if (bnd[0] > 0) r.lb = bnd[0];
+    if (bnd[1] > 0) r.tb = bnd[1];
+    r.check_actual();
+    return r;
+  }
+  static const Fp<P>& plain(const FpChecked<P>& a) { return a.v; }
+  static FpChecked<P> words(const uint32_t* w) { return FpChecked<P>::wrap(limbs_from_words<P>(w), 5.4); }
+  static FpChecked<P> from_ref(const uint32_t* w) { return Conv<FpChecked<P>>::in(w); }
+  static FpChecked<P> from_int(const uint32_t* w) { return mul(words(w), FpChecked<P>::from_const(P::C_INT_TO_MONT)); }
+  static void to_ref(const FpChecked<P>& a, uint32_t* w) { Conv<FpChecked<P>>::out(a, w); }
 };
+}  // namespace kgcase
+using namespace kgcase;
 
-template <class F> static F xsub(const F& a, const F& b) { return norm(sub<4, 1>(a, b)); }
-
-// op: 0 mul, 1 sqr, 2 add, 3 sub, 4 neg, 5 dbl, 6 inv, 7 (a*b+a*a) via lazy chain, 8 identity round trip, 9 inv by binary GCD
 template <class F>
 static void field_ops(int op, const uint32_t* a, const uint32_t* b, uint32_t* o, size_t n) {
   const int W = Conv<F>::W;
-  for (size_t i = 0; i < n; ++i) {
-    F x = Conv<F>::in(a + W * i), y = Conv<F>::in(b + W * i), r = x;
-    switch (op) {
-      case 0: r = mul(x, y); break;
-      case 1: r = sqr(x); break;
-      case 2: r = norm(add(x, y)); break;
-      case 3: r = xsub(x, y); break;
-      case 4: r = xsub(F::zero(), x); break;
-      case 5: r = norm(dbl(x)); break;
-      case 6: r = inv(x); break;
-      case 7: r = mul(norm(add(mul(x, y), sqr(x))), F::one()); break;
-      case 8: r = x; break;
-      case 9: r = inv_fast(x); break;          // binary-GCD inversion (fp_inv.h)
-    }
-    Conv<F>::out(r, o + W * i);
-  }
+  for (size_t i = 0; i < n; ++i) field_case<F>(op, a + W * i, b + W * i, o + W * i);
+}
+template <class F>
+static void raw_ops(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, const uint32_t* k, const double* bnd,
+                    uint32_t* out, size_t n) {
+  for (size_t i = 0; i < n; ++i) raw_case<F>(op, a + 9 * i, b + 9 * i, c + 9 * i, d + 9 * i, k + 18 * i, bnd, out + RAW_OUT * i);
+}
+template <class G>
+static void raw2_ops(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, const double* bnd, uint32_t* out, size_t n) {
+  for (size_t i = 0; i < n; ++i) raw2_case<G>(op, a + 18 * i, b + 18 * i, c + 18 * i, d + 18 * i, bnd, out + RAW_OUT * i);
+}
+template <class F>
+static void curve_ops(int op, const uint32_t* p, const uint32_t* q, uint32_t* o, uint8_t* inf, size_t n) {
+  const int W = Conv<F>::W;
+  for (size_t i = 0; i < n; ++i) inf[i] = (uint8_t)curve_case<F>(op, p + 4 * W * i, q + 4 * W * i, o + 2 * W * i);
 }
 
 // The HOST field type of the product (host_fp.h: 4 x 64-bit Montgomery words, the ABI form itself; the MSM's host finish and the
@@ -85,6 +91,20 @@ void ht_field_ops(int field, int checked, int op, const uint32_t* a, const uint3
   else if (field == 1) { if (checked) field_ops<FqC>(op, a, b, o, n); else field_ops<Fq>(op, a, b, o, n); }
   else { if (checked) field_ops<Fq2C>(op, a, b, o, n); else field_ops<Fq2>(op, a, b, o, n); }
 }
+// The raw-limb primitives of fp29.h one at a time (arith_cases.h: raw_case; the GPU runs the same lines through tests/device/devprobe.hip).
+// a, b, c, d: n x 9 limbs; k: n x 18 limbs of FpConst (R_MULC); out: n x 18 words.  field: 0 Fr, 1 Fq.  checked = 1: every operand is
+// wrapped as FpChecked with the bounds its class declares (bnd: {limb, top limb, K} for a, b, c, d): an operand outside a primitive's
+// documented precondition aborts the process.
+void ht_raw_ops(int field, int checked, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, const uint32_t* k,
+                const double* bnd, uint32_t* out, size_t n) {
+  if (field == 0) { if (checked) raw_ops<FrC>(op, a, b, c, d, k, bnd, out, n); else raw_ops<Fr>(op, a, b, c, d, k, nullptr, out, n); }
+  else { if (checked) raw_ops<FqC>(op, a, b, c, d, k, bnd, out, n); else raw_ops<Fq>(op, a, b, c, d, k, nullptr, out, n); }
+}
+// Fp2<Fq> on raw limbs (n x 18 per operand): op 0 mul, 1 sqr, 2 mul2sub, 3 inv
+void ht_raw2_ops(int checked, int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, const double* bnd, uint32_t* out,
+                 size_t n) {
+  if (checked) raw2_ops<FqC>(op, a, b, c, d, bnd, out, n); else raw2_ops<Fq>(op, a, b, c, d, nullptr, out, n);
+}
 void ht_hostfp_ops(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* o, size_t n) {
   if (field == 0) hostfp_ops<kg::HostFr>(op, a, b, o, n); else hostfp_ops<kg::HostFq>(op, a, b, o, n);
 }
@@ -106,18 +126,6 @@ static int st_aff(const XYZZ<F>& p, uint32_t* xy) {
   Conv<F>::out(a.x, xy); Conv<F>::out(a.y, xy + Conv<F>::W);
   return 0;
 }
-// a point in memory read and written coordinate by coordinate: the device's SoaSrc / SoaDst / AosSrc accessors over one slot
-template <class F> struct MemPt {
-  XYZZ<F>* s;
-  F x() const { return s->x; }
-  F y() const { return s->y; }
-  F zz() const { return s->zz; }
-  F zzz() const { return s->zzz; }
-  void x(const F& v) const { s->x = v; }
-  void y(const F& v) const { s->y = v; }
-  void zz(const F& v) const { s->zz = v; }
-  void zzz(const F& v) const { s->zzz = v; }
-};
 // The lane-cooperative addition / doubling of coop_add.h on the host: the step functions run lane by lane, step by step, over an "image"
 // that holds field elements of type F (the device's image holds their limbs; the bound-tracking type keeps its bounds this way).
 template <class F> struct HostQuad {
@@ -332,56 +340,60 @@ extern "C" int ht_curve_sum(int curve, int checked, int mode, const uint32_t* pt
   return checked ? curve_sum<Fq2C>(mode, pts, inf, n, out_xy) : curve_sum<Fq2>(mode, pts, inf, n, out_xy);
 }
 
-// signed window digits of canonical integers k (msm_digits.h): digits[i * 128 + w], w < W = ceil(255 / c) <= 128; returns W
+// one point formula of curve.h per element (arith_cases.h: curve_case): p, q = X | Y | ZZ | ZZZ in the ABI form, o = affine x | y, inf[i] = 1 for the identity
+extern "C" void ht_curve_ops(int curve, int checked, int op, const uint32_t* p, const uint32_t* q, uint32_t* o, uint8_t* inf, size_t n) {
+  if (curve == 0) { if (checked) curve_ops<FqC>(op, p, q, o, inf, n); else curve_ops<Fq>(op, p, q, o, inf, n); }
+  else if (curve == 1) { if (checked) curve_ops<FrC>(op, p, q, o, inf, n); else curve_ops<Fr>(op, p, q, o, inf, n); }
+  else { if (checked) curve_ops<Fq2C>(op, p, q, o, inf, n); else curve_ops<Fq2>(op, p, q, o, inf, n); }
+}
+
+// The lane-cooperative addition and doubling the way tests/device/devprobe.hip drives them on the GPU (k_coop): nwg images of COOP_ITEMS points, 16
+// parameter rows (ia, ib, io, active, doublings) per image; the quads of an image work on disjoint items, so one after the other here is what the
+// wave does at once there.  The register form of the steps (host_coop_add_regs / host_coop_dbl_regs).  Returns 1 for a row outside the image.
+template <class F>
+static int coop_ops(const uint32_t* items, const uint32_t* params, size_t nwg, uint32_t* o, uint8_t* inf) {
+  const int W = Conv<F>::W;
+  for (size_t g = 0; g < nwg; ++g) {
+    std::vector<XYZZ<F>> img;
+    for (uint32_t t = 0; t < COOP_ITEMS; ++t) img.push_back(xyzz_in<F>(items + (g * COOP_ITEMS + t) * 4 * W));
+    for (uint32_t t = 0; t < COOP_QUADS; ++t) {
+      const uint32_t* pr = params + (g * COOP_QUADS + t) * COOP_PARAMS;
+      if (!coop_params_ok(pr)) return 1;
+      if (pr[3]) host_coop_add_regs(img, pr[0], pr[1], pr[2]);
+      for (uint32_t k = 0; k < pr[4]; ++k) host_coop_dbl_regs(img, pr[2]);
+    }
+    for (uint32_t t = 0; t < COOP_ITEMS; ++t) inf[g * COOP_ITEMS + t] = (uint8_t)affine_out<F>(img[t], o + (g * COOP_ITEMS + t) * 2 * W);
+  }
+  return 0;
+}
+extern "C" int ht_coop_ops(int curve, int checked, const uint32_t* items, const uint32_t* params, size_t nwg, uint32_t* o, uint8_t* inf) {
+  if (curve == 0) return checked ? coop_ops<FqC>(items, params, nwg, o, inf) : coop_ops<Fq>(items, params, nwg, o, inf);
+  if (curve == 1) return checked ? coop_ops<FrC>(items, params, nwg, o, inf) : coop_ops<Fr>(items, params, nwg, o, inf);
+  return checked ? coop_ops<Fq2C>(items, params, nwg, o, inf) : coop_ops<Fq2>(items, params, nwg, o, inf);
+}
+
+// The digit helpers run the cases of arith_cases.h (the device runs the same lines).
 // GLV decomposition (msm_digits.h): k (canonical, 8 words each) -> |k1|, |k2| (4 words each) and their signs; field: 0 Fr, 1 Fq
 extern "C" void ht_glv_decompose(int field, const uint32_t* k, size_t n, uint32_t* k1, uint32_t* k2, uint8_t* neg) {
   for (size_t i = 0; i < n; ++i) {
-    bool n1, n2;
-    if (field == 0) kg::glv_decompose_with<kg::GlvLattice<kg::FrParams>>(k + 8 * i, k1 + 4 * i, n1, k2 + 4 * i, n2);
-    else kg::glv_decompose_with<kg::GlvLattice<kg::FqParams>>(k + 8 * i, k1 + 4 * i, n1, k2 + 4 * i, n2);
-    neg[2 * i] = n1; neg[2 * i + 1] = n2;
+    if (field == 0) glv_decompose_case<kg::GlvLattice<kg::FrParams>>(k + 8 * i, k1 + 4 * i, k2 + 4 * i, neg + 2 * i);
+    else glv_decompose_case<kg::GlvLattice<kg::FqParams>>(k + 8 * i, k1 + 4 * i, k2 + 4 * i, neg + 2 * i);
   }
 }
+// signed window digits of canonical integers k (msm_digits.h): digits[i * 128 + w], w < W = ceil(255 / c) <= 128; returns W
 extern "C" int ht_small_digits(const uint32_t* k, size_t n, int c, int32_t* digits) {
-  const int W = (255 + c - 1) / c;
-  uint32_t H[8];
-  small_bias(c, W, H);
-  for (size_t i = 0; i < n; ++i) {
-    uint32_t kb[8];
-    uint64_t cy = 0;
-    for (int j = 0; j < 8; ++j) { const uint64_t s_ = (uint64_t)k[8 * i + j] + H[j] + cy; kb[j] = (uint32_t)s_; cy = s_ >> 32; }
-    for (int w = 0; w < W; ++w) {
-      bool neg;
-      const uint32_t m = small_window_digit(kb, w, c, W, neg);
-      digits[i * 128 + w] = neg ? -(int32_t)m : (int32_t)m;
-    }
-  }
-  return W;
+  for (size_t i = 0; i < n; ++i) small_digits_case(k + 8 * i, c, digits + i * 128);
+  return (255 + c - 1) / c;
 }
 
 // The whole digit path of a scalar with halved scalars (glv): decomposition, |k_e| + H over W = ceil(128 / c) windows, signed digits with the
 // half's sign folded in.  digits: [n][2][64] (window w of half e); returns W.
 extern "C" int ht_glv_digits(int field, const uint32_t* k, size_t n, int c, int32_t* digits) {
-  const int W = (128 + c - 1) / c;
-  uint32_t H[8];
-  small_bias(c, W, H);
   for (size_t i = 0; i < n; ++i) {
-    uint32_t ks[2][8];
-    bool ng[2];
-    if (field == 0) kg::glv_decompose_with<kg::GlvLattice<kg::FrParams>>(k + 8 * i, ks[0], ng[0], ks[1], ng[1]);
-    else kg::glv_decompose_with<kg::GlvLattice<kg::FqParams>>(k + 8 * i, ks[0], ng[0], ks[1], ng[1]);
-    for (int e = 0; e < 2; ++e) {
-      uint64_t cy = 0;
-      for (int j = 0; j < 4; ++j) { const uint64_t s_ = (uint64_t)ks[e][j] + H[j] + cy; ks[e][j] = (uint32_t)s_; cy = s_ >> 32; }
-      for (int j = 4; j < 8; ++j) ks[e][j] = 0;
-      for (int w = 0; w < W; ++w) {
-        bool neg;
-        const uint32_t m = small_window_digit(ks[e], w, c, W, neg);
-        digits[(i * 2 + e) * 64 + w] = (neg != ng[e]) ? -(int32_t)m : (int32_t)m;
-      }
-    }
+    if (field == 0) glv_digits_case<kg::GlvLattice<kg::FrParams>>(k + 8 * i, c, digits + i * 128);
+    else glv_digits_case<kg::GlvLattice<kg::FqParams>>(k + 8 * i, c, digits + i * 128);
   }
-  return W;
+  return (128 + c - 1) / c;
 }
 
 // ---- NTT butterfly network (ntt_core.h) ---------------------------------------------------------------

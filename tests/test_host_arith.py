@@ -8,6 +8,7 @@ import random
 import numpy as np
 import pytest
 
+import primitive_cases as PC
 from helpers import CURVES, U8P, np_to_pt, p32, pt_to_np
 
 SEED = 0x4B6F676172617368
@@ -304,3 +305,178 @@ def test_glv_digit_path_recomposes_the_scalar(hostlib, pyoracle, c):
             k2 = sum(int(row[1][w]) << (w * c) for w in range(W))
             assert (k1 + k2 * lam - k) % n == 0
             assert all(abs(int(row[e][w])) <= 1 << (c - 1) for e in range(2) for w in range(W))
+
+
+# ---- the primitives one at a time: the CPU twins of tests/test_gpu_primitives.py -------------------------------------------------------------
+# The operand arrays, the exact-integer checkers and the branch census live in primitive_cases.py; the GPU tests send the same arrays through
+# tests/device/devprobe.hip and ask for the bits the plain host run returns here.
+
+
+@pytest.fixture(scope="module")
+def raw_batches(hostlib):
+    B = {fd: PC.raw_batches(fd) for fd in (0, 1)}
+    for fd in (0, 1):
+        for b in B[fd]["mulc"]:
+            PC.mulc_constants(hostlib, fd, b)
+    return B
+
+
+@pytest.mark.parametrize("fd", [0, 1])
+def test_raw_limb_primitives_meet_their_postconditions(hostlib, raw_batches, fd):
+    """every raw-limb primitive of fp29.h on every operand class: the congruence and the postcondition its comment promises, with the plain type;
+    then the same operands wrapped as FpChecked with the bounds the class declares -- an operand outside a documented precondition aborts the
+    process, so this run is what certifies the classes as legal -- and the same bits from it"""
+    total = 0
+    for prim, batches in raw_batches[fd].items():
+        for b in batches:
+            b.assert_declared(PC.MODS[fd], prim in PC.WORD_OPS)
+            out = PC.host_raw(hostlib, fd, 0, prim, b)
+            PC.check_batch(fd, prim, b, out)
+            if b.checked:
+                assert (PC.host_raw(hostlib, fd, 1, prim, b) == out).all(), (prim, b.name)
+            total += len(b)
+    assert total >= 4000, total
+
+
+@pytest.mark.parametrize("fd", [0, 1])
+def test_operands_reach_every_branch_class(raw_batches, fd):
+    """the branch census, from the exact integers of the operands alone (no library output): each class is met by at least 8 operands"""
+    cnt = PC.census(fd, raw_batches[fd])
+    assert all(v >= 8 for v in cnt.values()), cnt
+
+
+@pytest.mark.parametrize("fd", [0, 1])
+def test_checkers_reject_subtly_wrong_outputs(hostlib, raw_batches, fd):
+    """the checkers pass the host's correct outputs (the test above) and reject each mutant of one: a flipped bit in one limb, value + p where
+    the postcondition is a bound (on a row within one p of it; mulc: value + 2p, see below), a carry left in limb 3 (limb 3 + 2^29, limb 4 - 1:
+    the same value) where limbs below 2^29 are promised, norm included"""
+    p = PC.MODS[fd]
+    rejected, plus_p = 0, set()
+    for prim, batches in raw_batches[fd].items():
+        b = batches[0]
+        out = PC.host_raw(hostlib, fd, 0, prim, b)
+        nres = 1 if prim.startswith("is_") or prim == "same_limbs" else (18 if prim == "make_const" else (8 if prim in ("words_from_limbs", "to_ref", "ref_to_int", "int_to_ref") else 9))
+        mutants = []
+        for i in (0, len(b) // 2, len(b) - 1):
+            for limb, bit in ((0, 0), (nres // 2, 7 if nres > 1 else 0), (nres - 1, 0 if nres == 1 else 20)):
+                m = out[i].copy(); m[limb] ^= np.uint32(1 << bit)
+                mutants.append((i, m, "bit"))
+        if PC.value_bound(prim, b, p) is not None:                  # value + p on a row whose output lies within one p of the class's bound
+            for bb in batches:
+                o2 = out if bb is b else PC.host_raw(hostlib, fd, 0, prim, bb)
+                lim = PC.value_bound(prim, bb, p)
+                # mulc's documented bound (2 + K / 169) p is more than one p above anything it returns: the exact quotient leaves less than
+                # K p^2 / 2^261 < (K / 169) p, an estimate one short adds one p, so value + p never leaves the bound; its mutant is value + 2p, on
+                # a row whose estimate is one short (the classes "a q a few units above a multiple of 2^261")
+                add = 2 * p if prim == "mulc" else p
+                hit = [i for i in range(len(bb)) if PC.val(o2[i][:9]) + add >= lim]
+                if hit:
+                    m = o2[hit[0]].copy(); m[:9] = PC.limbs(PC.val(o2[hit[0]][:9]) + add)
+                    PC.check_raw(fd, prim, bb, hit[0], o2[hit[0]])
+                    with pytest.raises(AssertionError):
+                        PC.check_raw(fd, prim, bb, hit[0], m)
+                    rejected += 1
+                    plus_p.add(prim)
+                    break
+        if prim in PC.CARRY_FREE_OUT:
+            i = next(i for i in range(len(b)) if int(out[i][4]) >= 1 and int(out[i][3]) < (1 << 29))
+            m = out[i].copy(); m[3] += np.uint32(1 << 29); m[4] -= np.uint32(1)
+            mutants.append((i, m, "carry"))
+        for i, m, what in mutants:
+            PC.check_raw(fd, prim, b, i, out[i])
+            with pytest.raises(AssertionError):
+                PC.check_raw(fd, prim, b, i, m)
+            rejected += 1
+    assert rejected > 300
+    assert plus_p == {"mul", "sqr", "mul2add", "mul2sub", "mul2pm_pos", "mul2pm_neg", "mulc", "vred", "reduce_2p", "reduce", "from_ref", "from_int"}, plus_p
+
+
+def test_fq2_raw_primitives_meet_their_postconditions(hostlib):
+    """Fp2<Fq> mul, sqr, mul2sub, inv on raw limbs: both coordinates' congruences and bounds, the plain type and the checked one (same bits)"""
+    for op, batches in PC.raw2_batches().items():
+        for b in batches:
+            out = PC.host_raw2(hostlib, 0, op, b)
+            PC.check_batch2(op, b, out)
+            assert (PC.host_raw2(hostlib, 1, op, b) == out).all(), (op, b.name)
+
+
+@pytest.mark.parametrize("fd,n", [(0, 4096), (1, 4096), (2, 1024)])
+def test_both_inversions_on_specials_and_seeded_elements(hostlib, oracle, fd, n):
+    """inv_fast (fp_inv.h) == the Fermat inv == pow(a, -1, p) on every special value and n oracle-seeded elements: 0 -> 0, a * a^-1 = 1"""
+    a = PC.inversion_operands(oracle, fd, n)
+    want = PC.inversion_expected(fd, a)
+    assert (field_ops(hostlib, fd, 0, 9, a, a) == want).all()
+    assert (field_ops(hostlib, fd, 0, 6, a, a) == want).all()
+    m = 256
+    assert (field_ops(hostlib, fd, 1, 6, a[:m].copy(), a[:m].copy()) == want[:m]).all()
+    prod = field_ops(hostlib, fd, 0, 0, a, want)
+    one = np.zeros_like(a[0]); one[:4] = oracle.f_consts(1 if fd == 2 else fd)["r"]
+    nz = a.any(axis=1)
+    assert (prod[nz] == one).all() and not prod[~nz].any()
+
+
+@pytest.mark.parametrize("name", ["g1", "gk", "g2"])
+def test_one_lane_point_formulas_one_at_a_time(hostlib, pyoracle, name):
+    """each formula of curve.h alone -- two operands in, one result out through to_affine -- on A+B, A+A, A+(-A), O+A, A+O, O+O, 2A+(-A), with the
+    XYZZ operands at Z = 1 and at random Z; the streaming forms in place on their first operand"""
+    cid, cur, _ = CURVES[name]
+    for opname, op in PC.CURVE_OPS.items():
+        p, q, want, names = PC.curve_case_arrays(cur, opname)
+        for chk in (0, 1):
+            o, inf = PC.host_curve_ops(hostlib, cid, chk, op, p, q)
+            for i in range(len(want)):
+                assert np_to_pt(cur, o[i], inf[i]) == want[i], (name, opname, names[i], i, chk)
+
+
+@pytest.mark.parametrize("name", ["g1", "gk", "g2"])
+def test_cooperative_levels_over_mixed_waves(hostlib, pyoracle, name):
+    """coop_add.h in the register form of its steps, 16 quads per image, each with its own (ia, ib, io, active, doublings): results in a third item
+    and in place on either operand, 0..3 doublings, idle quads, and every item of the image compared (an item no quad owns must not change)"""
+    cid, cur, _ = CURVES[name]
+    items, params, want, kinds = PC.coop_waves(cur)
+    PC.assert_coop_waves_are_mixed(kinds)
+    for chk in (0, 1):
+        o, inf = PC.host_coop_ops(hostlib, cid, chk, items, params)
+        for i in range(len(want)):
+            assert np_to_pt(cur, o[i], inf[i]) == want[i], (name, i // PC.COOP_ITEMS, (i % PC.COOP_ITEMS) // 3, chk)
+
+
+@pytest.mark.parametrize("fd", [0, 1])
+def test_glv_decomposition_at_its_rounding_boundaries(hostlib, pyoracle, fd):
+    """glv_decompose_with at the edge scalars and at the scalars where c_i = (G_i k + 2^255) >> 256 steps from j to j + 1 (the first such k and
+    its neighbours, for j = 0, 1, 2, 12345 and the last step below n, both G_i): 30 of them per lattice, every half below 3 * 2^125"""
+    curve = pyoracle.G1 if fd == 0 else pyoracle.GRUMPKIN
+    n, lam = curve.n, PC.glv_module().consts(curve)[0]
+    edges, bound, rand = PC.glv_edge_scalars(fd, n, lam)
+    assert len(bound) == 30
+    g = PC.lattice_g(fd)
+    for i, gi in enumerate(g):                                              # the boundary scalars are boundaries: c_i differs across them
+        ci = lambda k: (gi * k + (1 << 255)) >> 256
+        assert sum(1 for k in bound if k + 1 < n and ci(k) != ci(k - 1)) >= 5, i
+    ks = edges + bound + rand
+    k1, k2, neg = PC.glv_decompose(hostlib.ht_glv_decompose, fd, ks)
+    PC.check_glv_halves(ks, k1, k2, neg, lam, n)
+    # and the halved digit path at the same edge and boundary scalars, every window width: the digits recompose, |digit| <= 2^(c-1)
+    eb = edges + bound
+    kw = PC.kwords(eb)
+    for c in range(2, 17):
+        dig = np.zeros((len(eb), 2, 64), dtype=np.int32)
+        hostlib.ht_glv_digits.restype = C.c_int
+        W = hostlib.ht_glv_digits(fd, p32(kw), C.c_size_t(len(eb)), c, dig.ctypes.data_as(C.POINTER(C.c_int32)))
+        assert W == (128 + c - 1) // c
+        PC.check_glv_digits(eb, dig, W, c, lam, n)
+
+
+def test_device_probe_library_cross_compiles_and_exports_every_entry():
+    """tests/device/devprobe.hip builds for gfx950 with the product's flags (no GPU needed) and exports what tests/test_gpu_primitives.py calls"""
+    import shutil
+    if shutil.which("hipcc") is None:
+        pytest.skip("no hipcc on PATH")
+    from kogarashi_amd import build as kb
+    so = kb.build_devprobe()
+    try:
+        import torch  # noqa: F401      (first, so that the process has one HIP runtime: kogarashi_amd/lib.py load())
+    except ImportError:
+        pass
+    dev = C.CDLL(so)
+    assert [e for e in PC.DEV_EXPORTS if not hasattr(dev, e)] == []
