@@ -126,6 +126,23 @@ inline G1Projective msm_curve_addition(const Context& c, const std::vector<G1Aff
   return r;
 }
 
+// Group::is_on_curve (zkstd/src/macros/curve/weierstrass/group.rs:59-65) and, for G2 with subgroup = true, [r]P = O (the call site of
+// bn254/src/g2.rs:26 is_torsion_free) over a whole slice: kg_points_check on an uploaded copy.  What a host runs on points it has no reason
+// to trust before it registers them.  status: per-point KG_PT_* bits (0 = valid), filled when non-null.
+struct PointsCheck { size_t bad, first_bad; };
+template <class Pt>
+inline PointsCheck check_points(const Context& c, const std::vector<Pt>& pts, int curve, bool subgroup = true, std::vector<uint8_t>* status = nullptr) {
+  std::vector<uint64_t> xy;
+  std::vector<uint8_t> inf;
+  detail::marshal(pts, pts.size(), xy, inf);
+  DeviceBuffer d(c, xy.data(), xy.size() * 8), di(c, inf.data(), inf.size()), ds(c, pts.size());
+  PointsCheck r{0, 0};
+  c.check(kg_points_check(c.raw(), curve, d.as<uint64_t>(), di.as<uint8_t>(), pts.size(), KG_CHECK_CURVE | (subgroup ? KG_CHECK_SUBGROUP : 0),
+                          ds.as<uint8_t>(), &r.bad, &r.first_bad), "kg_points_check");
+  if (status) { status->resize(pts.size()); ds.download(status->data()); }
+  return r;
+}
+
 // The same call against bases that stay on the device: what a Rust host does behind `msm_curve_addition` for a CRS vector or any
 // other slice it meets again (rust/kogarashi-amd/src/lib.rs: register_bases / the address-keyed cache) -- marshal, upload and
 // kg_bases_register ONCE, then every call moves only its scalars (kg_msm_host_scalars: index slices uploaded under the accumulations).
@@ -313,6 +330,13 @@ class Prover {
     c_.check(kg_groth16_prove_bn254(c_.raw(), &crs_, da.as<uint64_t>(), db.as<uint64_t>(), dc.as<uint64_t>(), dx.as<uint64_t>(), dw.as<uint64_t>(),
                                     r.data(), s.data(), out, inf), "kg_groth16_prove_bn254");
     return {detail::g1_from(out, inf[0] != 0), detail::g2_from(out + 8, inf[1] != 0), detail::g1_from(out + 24, inf[2] != 0)};
+  }
+  // kg_groth16_crs_check over the resident CRS: the counts of invalid points in the order h, l, a, b_g1, b_g2, alpha_g1, beta_g1, delta_g1,
+  // beta_g2, delta_g2 -- all zero for Parameters to trust
+  std::array<size_t, 10> check_crs(bool subgroup = true) const {
+    std::array<size_t, 10> bad{};
+    c_.check(kg_groth16_crs_check(c_.raw(), &crs_, KG_CHECK_CURVE | (subgroup ? KG_CHECK_SUBGROUP : 0), bad.data()), "kg_groth16_crs_check");
+    return bad;
   }
 
  private:

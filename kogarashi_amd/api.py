@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .lib import KG_FQ, KG_FR, KG_G1, KG_G2, KG_GRUMPKIN, Context, Groth16Crs
+from .lib import KG_CHECK_CURVE, KG_CHECK_SUBGROUP, KG_FQ, KG_FR, KG_G1, KG_G2, KG_GRUMPKIN, Context, Groth16Crs
 
 _default_ctx = None
 CURVE_IDS = {"g1": KG_G1, "grumpkin": KG_GRUMPKIN, "gk": KG_GRUMPKIN, "g2": KG_G2}
@@ -39,6 +39,23 @@ def msm_curve_addition(bases, coeffs, curve="g1", is_infinity=None, ctx: Context
     if is_infinity is not None:
         inf = np.ascontiguousarray(is_infinity, dtype=np.uint8)[:n]
     return ctx.msm_host(cid, bases[:n], inf, coeffs[:n], n)
+
+
+def check_points(points, curve="g1", is_infinity=None, subgroup=True, ctx: Context | None = None) -> np.ndarray:
+    """Status byte per point (kg_points_check): 0 = valid, KG_PT_NON_CANONICAL, KG_PT_OFF_CURVE, KG_PT_NOT_IN_SUBGROUP (G2 with
+    subgroup=True: [r]P != O).  The reference's Group::is_on_curve / is_torsion_free (group.rs:59-65, bn254/src/g2.rs:26) over a whole
+    array; what a host runs on a key or CRS of unknown origin before it hands it to PedersenCommitment / Prover."""
+    ctx = ctx or default_context()
+    cid = CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, _LIMBS[cid])
+    n = len(pts)
+    if n == 0:
+        return np.zeros(0, dtype=np.uint8)
+    d = ctx.upload(pts)
+    di = ctx.upload(np.ascontiguousarray(is_infinity, dtype=np.uint8)[:n]) if is_infinity is not None else None
+    st = ctx.empty((n,), dtype=np.uint8)
+    ctx.points_check(cid, d.ptr, di.ptr if di else 0, n, KG_CHECK_CURVE | (KG_CHECK_SUBGROUP if subgroup else 0), st.ptr)
+    return st.numpy()
 
 
 class Fft:
@@ -104,6 +121,12 @@ class PedersenCommitment:
         except Exception:
             pass
 
+    def check(self, subgroup: bool = True) -> tuple[int, int]:
+        """(bad, first_bad) of kg_points_check over the resident generators: (0, len) for a key every point of which is on the curve
+        (and, for G2 with subgroup=True, in the order-r subgroup)"""
+        return self.ctx.points_check(self.cid, self._g.ptr, self._inf.ptr if self._inf else 0, self.len,
+                                     KG_CHECK_CURVE | (KG_CHECK_SUBGROUP if subgroup else 0))
+
     def commit(self, m):
         m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1, 4)
         n = min(len(m), self.len)
@@ -166,6 +189,10 @@ class Prover:
                 self.ctx.bases_unregister(p_)
             except Exception:
                 pass
+
+    def check_crs(self, subgroup: bool = True) -> dict:
+        """kg_groth16_crs_check over the resident CRS: {member: number of invalid points}, all zero for a CRS to trust"""
+        return self.ctx.groth16_crs_check(self.crs, KG_CHECK_CURVE | (KG_CHECK_SUBGROUP if subgroup else 0))
 
     def create_proof(self, a_eval, b_eval, c_eval, x, w, r, s):
         """Proof {a, b, c} for the synthesised constraint system: (A, B, C) = cs.evaluate(), x = cs.x(), w = cs.w();

@@ -410,6 +410,7 @@ void kg_ctx_destroy(kg_ctx* c) {
   for (void* b : c->up_buf) if (b) hipFree(b);
   for (uint32_t* t : c->fb_table) if (t) hipFree(t);
   if (c->fb_tmp) hipFree(c->fb_tmp);
+  if (c->ws_points) hipFree(c->ws_points);
   if (c->up_stream) { hipStreamSynchronize(c->up_stream); hipStreamDestroy(c->up_stream); }
   for (int i = 0; i < kg_ctx::UP_SLICES; ++i) { if (c->ev_up_s[i]) hipEventDestroy(c->ev_up_s[i]); if (c->ev_up_b[i]) hipEventDestroy(c->ev_up_b[i]); }
   for (auto& r : c->registered) { hipFree(r.packed); if (r.table) hipFree(r.table); }

@@ -100,6 +100,7 @@ struct kg_ctx {
   hipStream_t up_stream = nullptr;
   static constexpr int UP_SLICES = 8;    // index slices of a host-array MSM (kg_msm_host, kg_msm_host_scalars): result slots 16 .. 23
   hipEvent_t ev_up_s[UP_SLICES] = {}, ev_up_b[UP_SLICES] = {};
+  void* ws_points = nullptr;             // kg_points_check (points.hip): the two summary words and the five host points of a CRS check
   void* fb_tmp = nullptr;                // XYZZ results between the two passes of kg_fixed_base_mul (grow-only)
   size_t fb_tmp_bytes = 0;
   uint32_t* fb_table[3] = {nullptr, nullptr, nullptr};   // kg_fixed_base_mul: 32 x 255 generator multiples d * 2^(8w) * G per curve, resident form

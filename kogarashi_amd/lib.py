@@ -16,6 +16,9 @@ SO_PATH = os.environ.get("KG_LIB_PATH", SO_PATH)     # A/B experiments: an alter
 
 KG_FR, KG_FQ = 0, 1
 KG_G1, KG_GRUMPKIN, KG_G2 = 0, 1, 2
+KG_CHECK_CURVE, KG_CHECK_SUBGROUP = 1, 2                                # `checks` mask of kg_points_check
+KG_PT_NON_CANONICAL, KG_PT_OFF_CURVE, KG_PT_NOT_IN_SUBGROUP = 1, 2, 4   # per-point status bits
+CRS_CHECK_MEMBERS = ("h", "l", "a", "b_g1", "b_g2", "alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")
 OPS = {"add": 0, "sub": 1, "mul": 2, "square": 3, "neg": 4, "double": 5, "invert": 6, "from_mont": 7, "to_mont": 8}
 EXPORTS = [
     "kg_version", "kg_init", "kg_hw_queue_setting", "kg_device_count", "kg_strerror", "kg_ctx_create", "kg_ctx_destroy", "kg_last_error", "kg_ctx_set_stream",
@@ -27,6 +30,7 @@ EXPORTS = [
     "kg_sharded_key_len", "kg_sharded_key_commit", "kg_r1cs_prod", "kg_nova_cross_term", "kg_ctx_set_inputs_complete", "kg_bases_precompute", "kg_msm_table_window", "kg_groth16_prove_r1cs_bn254", "kg_groth16_prove_r1cs_begin", "kg_groth16_prove_sharded", "kg_ntt_plan",
     "kg_msm_host_scalars", "kg_commit_host_scalars", "kg_tuning_describe", "kg_mem_info", "kg_groth16_setup_bn254", "kg_experiments_built", "kg_msm_host_slices",
     "kg_msm_set_small", "kg_ctx_worker_threads", "kg_ctx_queue_placement2", "kg_ctx_trim",
+    "kg_points_check", "kg_groth16_crs_check",
 ]
 
 
@@ -83,6 +87,11 @@ def load():
         _lib.kg_sharded_key_len.argtypes = [C.c_void_p]
         _lib.kg_sharded_key_destroy.argtypes = [C.c_void_p]
         _lib.kg_sharded_key_destroy.restype = None
+        _lib.kg_points_check.restype = C.c_int
+        _lib.kg_points_check.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        _lib.kg_groth16_crs_check.restype = C.c_int
+        _lib.kg_groth16_crs_check.argtypes = [C.c_void_p, C.POINTER(Groth16Crs), C.c_int, C.POINTER(C.c_size_t)]
     return _lib
 
 
@@ -263,6 +272,20 @@ class Context:
 
     def bases_unregister(self, bases: int):
         self._chk(self._lib.kg_bases_unregister(self._h, _vp(bases)), "kg_bases_unregister")
+
+    def points_check(self, curve: int, xy: int, inf: int, n: int, checks: int, status: int = 0) -> tuple[int, int]:
+        """kg_points_check: (number of points with a non-zero status, smallest such index or n); xy / inf / status are device pointers
+        (inf, status may be 0); checks = KG_CHECK_CURVE | KG_CHECK_SUBGROUP.  Blocks."""
+        bad, first = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self._lib.kg_points_check(self._h, int(curve), _vp(xy), _vp(inf), C.c_size_t(n), int(checks), _vp(status), C.byref(bad), C.byref(first)),
+                  "kg_points_check")
+        return int(bad.value), int(first.value)
+
+    def groth16_crs_check(self, crs: "Groth16Crs", checks: int) -> dict:
+        """kg_groth16_crs_check: {member: number of points with a non-zero status} over h, l, a, b_g1, b_g2 and the five host points"""
+        out = (C.c_size_t * 10)()
+        self._chk(self._lib.kg_groth16_crs_check(self._h, C.byref(crs), int(checks), out), "kg_groth16_crs_check")
+        return {name: int(out[i]) for i, name in enumerate(CRS_CHECK_MEMBERS)}
 
     def msm_begin(self, curve: int, bases: int, inf: int, scalars: int, n: int, ticket: int):
         self._chk(self._lib.kg_msm_begin(self._h, curve, _vp(bases), _vp(inf), _vp(scalars), C.c_size_t(n), int(ticket)), "kg_msm_begin")

@@ -76,6 +76,14 @@ pub const KG_G1: i32 = 0;
 pub const KG_GRUMPKIN: i32 = 1;
 pub const KG_G2: i32 = 2;
 
+// kg_points_check: the `checks` mask and the per-point status bits
+pub const KG_CHECK_CURVE: i32 = 1;
+pub const KG_CHECK_SUBGROUP: i32 = 2;
+pub const KG_PT_NON_CANONICAL: i32 = 1;
+pub const KG_PT_OFF_CURVE: i32 = 2;
+/// G2 only: `[r]P != O`
+pub const KG_PT_NOT_IN_SUBGROUP: i32 = 4;
+
 // kg_field_op
 pub const KG_OP_ADD: i32 = 0;
 pub const KG_OP_SUB: i32 = 1;

@@ -458,6 +458,25 @@ pub fn register_bases<C: GpuCurve>(bases: &[C]) -> Option<ResidentMsmBases> {
     Some(ResidentMsmBases(Some(Resident::upload(&ctx, bases, digest(bases, 1))?)))
 }
 
+/// `is_on_curve` over a whole slice (group.rs:59-65) and, with `subgroup`, `[r]P = O` for G2 (the call site of
+/// `G2Affine::is_torsion_free`, bn254/src/g2.rs:26): `kg_points_check` on an uploaded copy.  Returns (number of invalid points, index
+/// of the first one or `points.len()`); `None` when the backend is unavailable.  What a host runs on deserialised `Parameters` or a
+/// commitment key before `register_bases`.
+pub fn points_check<C: GpuCurve>(points: &[C], subgroup: bool) -> Option<(usize, usize)> {
+    if points.is_empty() {
+        return Some((0, 0));
+    }
+    let ctxs = contexts()?;
+    let ctx = ctxs.lock(0)?;
+    let (xy, inf) = marshal(points);
+    let d_xy = DeviceBuf::from_words(&ctx, &xy).ok()?;
+    let d_inf = DeviceBuf::from_bytes(&ctx, &inf).ok()?;
+    let checks = sys::KG_CHECK_CURVE | if subgroup { sys::KG_CHECK_SUBGROUP } else { 0 };
+    let (mut bad, mut first) = (0usize, 0usize);
+    let rc = unsafe { sys::kg_points_check(ctx.raw(), C::CURVE, d_xy.as_u64() as *const u64, d_inf.as_u8() as *const u8, points.len(), checks, ptr::null_mut(), &mut bad, &mut first) };
+    if rc == sys::KG_OK { Some((bad, first)) } else { None }
+}
+
 const MSM_CACHE_SLOTS: usize = 8;
 static MSM_BASES: Mutex<Option<(u64, HashMap<(usize, usize, i32), Resident>)>> = Mutex::new(None);
 
