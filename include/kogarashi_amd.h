@@ -390,6 +390,24 @@ int kg_r1cs_prod(kg_ctx* ctx, int field, const uint64_t* d_row_ptr, const uint64
  * read once, the six products stay in registers. */
 int kg_nova_cross_term(kg_ctx* ctx, int field, const kg_csr* a, const kg_csr* b, const kg_csr* c, size_t m, const uint64_t* d_z1,
                        const uint64_t* d_z2, const uint64_t* h_u1, const uint64_t* h_u2, uint64_t* d_out);
+/* ---- R1CS satisfiability ----------------------------------------------------------------------------
+ * Does z satisfy the constraints?  Row i holds iff (A z)_i * (B z)_i = u * (C z)_i + E_i (mod p), field = KG_FR or KG_FQ.  With h_u and d_e
+ * both NULL this is R1cs::is_sat (zkstd/src/r1cs.rs:62-77) and the constraint half of R1csShape::is_sat (nova/src/relaxed_r1cs.rs:117-146;
+ * its other half, commit_w == ck.commit(w), is a kg_commit the caller compares); with both given it is is_sat_relaxed
+ * (relaxed_r1cs.rs:81-114) -- what the reference asserts around every fold (nova/src/prover.rs:163-165, verifier.rs:62, proof.rs:71-75).
+ * No prover entry of this library runs it: kg_groth16_prove_r1cs_bn254 divides a o b - c by Z whether or not it is a multiple of Z (an
+ * unsatisfied witness yields a well-formed proof no verifier accepts), the Nova folds fold what they are given.
+ * a, b, c: CSR with m rows.  PRECONDITION, as for kg_r1cs_prod and kg_nova_cross_term and not tested here either: row_ptr ascends from its
+ * first entry, every column index lies inside d_z, coefficients and vector entries are canonical Montgomery values.  d_z: DEVICE, the vector
+ * the columns index -- (u | x | w) for Nova, x || w with x[0] = 1 for Groth16.  h_u: HOST, one element; NULL: u = 1.  d_e: DEVICE, m elements;
+ * NULL: E = 0 (nothing is read).  d_status: DEVICE, m bytes, may be NULL: 0 or KG_ROW_UNSAT per row.  *out_bad: the number of rows with a
+ * non-zero status; *out_first_bad: the smallest such row, m when there is none (either may be NULL).
+ * Runs on the context's stream behind whatever was enqueued (a kg_field_vec_axpy fold just before it is seen) and blocks: it reads two
+ * words back.  The return value says whether the check RAN: KG_OK whatever it found.  m == 0: KG_OK, 0 / 0.  m >= 2^32: KG_ERR_BAD_ARG.
+ * Exact and deterministic.  One pass: every matrix row is read once, the three row sums and the residual stay in registers. */
+enum { KG_ROW_UNSAT = 1 };   /* per-row status */
+int kg_r1cs_check(kg_ctx* ctx, int field, const kg_csr* a, const kg_csr* b, const kg_csr* c, size_t m, const uint64_t* d_z,
+                  const uint64_t* h_u, const uint64_t* d_e, uint8_t* d_status, size_t* out_bad, size_t* out_first_bad);
 /* create_proof with cs.evaluate() (zkstd/src/r1cs.rs:137-142, prover.rs:33) on the device as well: the constraint matrices
  * a, b, c (CSR over z = x || w, m = crs->m rows; resident, uploaded once per circuit) take the place of the three
  * evaluation vectors -- each transform chain starts with its matrix-vector product.  Otherwise as kg_groth16_prove_bn254 /

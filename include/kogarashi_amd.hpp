@@ -7,6 +7,7 @@
 //   PedersenCommitment(g).commit(m)                                      nova/src/pedersen.rs:6-20
 //   Prover(params).create_proof(a, b, c, x, w, r, s)                     groth16/src/prover.rs:14-99
 //   R1csShape(a, b, c).prod / compute_cross_term(z1, z2, u1, u2)         zkstd/src/matrix.rs:36-48, nova/src/prover.rs:53-90
+//   R1csShape(a, b, c).is_sat(z) / is_sat_relaxed(z, u, e)              zkstd/src/r1cs.rs:62-77, nova/src/relaxed_r1cs.rs:81-146
 //   ShardedPedersenCommitment(ctxs, g).commit(m)                         nova/src/pedersen.rs:6-20 over every GPU of the node
 //
 // with the reference's in-memory data: a field element is 4 x uint64 Montgomery limbs (Fr / Fq), an affine point x | y plus an
@@ -465,8 +466,31 @@ class R1csShape {
     out.download(t.data());
     return t;
   }
+  // R1cs::is_sat (zkstd/src/r1cs.rs:62-77) and the constraint half of R1csShape::is_sat (nova/src/relaxed_r1cs.rs:117-146): AZ o BZ = CZ;
+  // is_sat_relaxed (relaxed_r1cs.rs:81-114): AZ o BZ = u CZ + E.  One kg_r1cs_check each: bad = the number of rows that do not hold,
+  // first_bad = the smallest of them (m() when bad == 0).  status: per-row 0 / KG_ROW_UNSAT, filled when non-null.
+  struct Sat {
+    size_t bad, first_bad;
+    explicit operator bool() const { return bad == 0; }
+  };
+  Sat is_sat(const std::vector<Fe>& z, std::vector<uint8_t>* status = nullptr) const { return check(z, nullptr, nullptr, status); }
+  Sat is_sat_relaxed(const std::vector<Fe>& z, const Fe& u, const std::vector<Fe>& e, std::vector<uint8_t>* status = nullptr) const {
+    if (e.size() != m_) throw std::invalid_argument("R1csShape: E has one element per constraint");
+    return check(z, &u, &e, status);
+  }
 
  private:
+  Sat check(const std::vector<Fe>& z, const Fe* u, const std::vector<Fe>* e, std::vector<uint8_t>* status) const {
+    covers(z);
+    DeviceBuffer dz(c_, z.data(), z.size() * 32), ds(c_, m_ ? m_ : 1);
+    std::unique_ptr<DeviceBuffer> de;
+    if (e && m_) de.reset(new DeviceBuffer(c_, e->data(), m_ * 32));
+    Sat r{0, 0};
+    c_.check(kg_r1cs_check(c_.raw(), field_, &csr_[0], &csr_[1], &csr_[2], m_, dz.as<uint64_t>(), u ? u->data() : nullptr,
+                           de ? de->as<uint64_t>() : nullptr, status ? ds.as<uint8_t>() : nullptr, &r.bad, &r.first_bad), "kg_r1cs_check");
+    if (status) { status->resize(m_); if (m_) ds.download(status->data()); }
+    return r;
+  }
   void covers(const std::vector<Fe>& z) const {          // the reference would panic on an index past z; the kernels do not check
     if (m_ && z.size() <= max_col_) throw std::out_of_range("R1csShape: z is shorter than the largest column index");
   }

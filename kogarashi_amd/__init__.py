@@ -6,5 +6,5 @@ There is no CPU implementation in this package: without the built HIP library an
 
 from . import lib  # noqa: F401
 from .lib import (KG_CHECK_CURVE, KG_CHECK_SUBGROUP, KG_PT_NON_CANONICAL, KG_PT_NOT_IN_SUBGROUP, KG_PT_OFF_CURVE,  # noqa: F401
-                  KG_FQ, KG_FR, KG_G1, KG_G2, KG_GRUMPKIN, Context, DeviceArray, KogarashiError, init, load)  # noqa: F401
+                  KG_FQ, KG_FR, KG_G1, KG_G2, KG_GRUMPKIN, KG_ROW_UNSAT, Context, DeviceArray, KogarashiError, init, load)  # noqa: F401
 from .api import Fft, NovaProver, PedersenCommitment, Prover, ShardedProver, check_points, msm_curve_addition, default_context  # noqa: F401

@@ -213,6 +213,15 @@ class Prover:
                              self.ctx.upload(col if len(col) else np.zeros(1, dtype=np.uint64)),
                              self.ctx.upload(val if len(val) else np.zeros((1, 4), dtype=np.uint64))))
 
+    def check_witness(self, x, w) -> tuple[int, int]:
+        """R1cs::is_sat (zkstd/src/r1cs.rs:62-77) for z = x || w against the attached constraint system: (number of violated constraints,
+        index of the first or m).  create_proof_from_witness does not run it: for a witness that violates a constraint it returns a
+        well-formed proof that no verifier accepts."""
+        up = lambda v: np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4)
+        dz = self.ctx.upload(np.concatenate([up(x), up(w)]))
+        ptrs = [tuple(d.ptr for d in trip) for trip in self._cs]
+        return self.ctx.r1cs_check(KG_FR, ptrs[0], ptrs[1], ptrs[2], self.m, dz.ptr)
+
     def create_proof_from_witness(self, x, w, r, s):
         """create_proof from (x, w) alone: the evaluation vectors are made on the device (kg_groth16_prove_r1cs_bn254)"""
         up = lambda v: self.ctx.upload(np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4))
@@ -426,6 +435,33 @@ class NovaProver:
         instance = {"commit_w": fold_point(instance1["commit_w"], instance2["commit_w"]),
                     "commit_e": fold_point(instance1["commit_e"], commit_t), "u": ux[0].copy(), "x": ux[1:].copy()}
         return instance, {"w": dw1.numpy(), "e": de1.numpy()}, commit_t
+
+    def check(self, u, x, w, e=None) -> tuple[int, int]:
+        """(bad, first_bad) of kg_r1cs_check over z = (u | x | w): the rows i with (A z)_i (B z)_i != u (C z)_i + E_i and the first of
+        them (m when there is none).  e: (m, 4) host array, a DeviceArray (e.g. a fold's output, still in flight on the context's
+        stream), or None for E = 0."""
+        z = self._z(u, x, w)
+        de = None
+        if e is not None:
+            de = e if hasattr(e, "ptr") else self.ctx.upload(np.ascontiguousarray(e, dtype=np.uint64).reshape(-1, 4))
+        ptrs = [tuple(d.ptr for d in trip) for trip in self._dev]
+        return self.ctx.r1cs_check(self.field, ptrs[0], ptrs[1], ptrs[2], self.m, z.ptr, u, de.ptr if de is not None else 0)
+
+    def is_sat_relaxed(self, instance: dict, witness: dict) -> bool:
+        """R1csShape::is_sat_relaxed (nova/src/relaxed_r1cs.rs:81-114) on the dicts prove() takes and returns: AZ o BZ = u CZ + E.
+        Like the reference it leaves the commitments alone."""
+        return self.check(instance["u"], instance["x"], witness["w"], witness["e"])[0] == 0
+
+    def is_sat(self, instance: dict, witness: dict) -> bool:
+        """R1csShape::is_sat (relaxed_r1cs.rs:117-146) for a fresh pair {"commit_w", "x"}, {"w"}: the constraints with u = 1, E = 0 and
+        instance.commit_w == ck.commit(witness.w)"""
+        if self.check(self._one(), instance["x"], witness["w"])[0] != 0:
+            return False
+        xy, inf = self.ck.commit(witness["w"])
+        wxy, winf = instance["commit_w"]
+        if bool(inf) or bool(winf):
+            return bool(inf) == bool(winf)
+        return bool((np.asarray(xy, dtype=np.uint64).reshape(-1) == np.asarray(wxy, dtype=np.uint64).reshape(-1)).all())
 
     def commit_t(self, u1, x1, w1, u2, x2, w2):
         """(T, commit_T): the cross term and ck.commit(&t) (prover.rs:33-35); T never leaves the device in between"""

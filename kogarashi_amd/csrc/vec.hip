@@ -271,6 +271,80 @@ __global__ void __launch_bounds__(256) k_nova_cross_term_long(CsrView A, CsrView
   }
 }
 
+// kg_r1cs_check: is (A z)_i (B z)_i = u (C z)_i + E_i for every row?  (nova/src/relaxed_r1cs.rs:81-114 is_sat_relaxed; u = 1 and E = 0:
+// zkstd/src/r1cs.rs:62-77 is_sat.)  The shape of the cross term with one z vector: a lane per row, the three row sums stay in registers,
+// rows with more than SHORT_ROW entries in any matrix go to the work list and get a wave each in the second launch.  Instead of an
+// element per row the kernels leave a status byte (when asked) and two summary words: per wave one ballot, and -- only for a wave that
+// holds a bad row -- one atomicAdd of the popcount and one atomicMin of the lowest bad row.  summary[0] = count, summary[1] = first index,
+// set to (0, m) on the stream by k_r1cs_check_init before every call (row indices are below 2^32).
+// us: u * 2^266 as limbs (host-side, like the cross term's).  e == nullptr: E = 0, nothing is read.
+__global__ void k_r1cs_check_init(uint32_t* long_count, uint32_t* summary, uint32_t m) {
+  long_count[0] = 0;
+  summary[0] = 0;
+  summary[1] = m;
+}
+template <class P>
+__device__ __forceinline__ bool row_unsat(const Fp<P>& az, const Fp<P>& bz, const Fp<P>& cz, const Limbs9& us, const uint64_t* __restrict__ e, size_t row) {
+  Fp<P> er = Fp<P>::zero();
+  if (e != nullptr) {
+    uint32_t we[8];
+    load_words(e, row, we);
+    er = limbs_from_words<P>(we);
+  }
+  return !is_zero_mod_p(sat_residual_row(az, bz, cz, Fp<P>::from_const(us.l), er, Fp<P>::from_const(P::C_XT_HAD)));
+}
+template <class P>
+__global__ void __launch_bounds__(256) k_r1cs_check(CsrView A, CsrView B, CsrView C, size_t m, const uint64_t* __restrict__ z, Limbs9 us,
+                                                    const uint64_t* __restrict__ e, uint8_t* __restrict__ status, uint32_t* __restrict__ summary,
+                                                    uint32_t* __restrict__ long_rows, uint32_t* __restrict__ long_count) {
+  KG_SERVICE_PRIO();
+  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;                                       // lanes past the end and lanes whose row went to the work list report nothing
+  if (row < m) {
+    if (A.row_ptr[row + 1] - A.row_ptr[row] > SHORT_ROW || B.row_ptr[row + 1] - B.row_ptr[row] > SHORT_ROW || C.row_ptr[row + 1] - C.row_ptr[row] > SHORT_ROW) {
+      long_rows[atomicAdd(long_count, 1u)] = (uint32_t)row;
+    } else {
+      Fp<P> az[1], bz[1], cz[1];
+      row_dot<P, 1, 1>(A.row_ptr, A.col, A.val, row, 0, z, z, az);
+      row_dot<P, 1, 1>(B.row_ptr, B.col, B.val, row, 0, z, z, bz);
+      row_dot<P, 1, 1>(C.row_ptr, C.col, C.val, row, 0, z, z, cz);
+      bad = row_unsat<P>(az[0], bz[0], cz[0], us, e, row);
+      if (status != nullptr) status[row] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
+    }
+  }
+  const unsigned long long mask = __ballot(bad);          // this wave's 64 rows
+  if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) {       // the lowest bad lane speaks for its wave: its row is the wave's first
+    atomicAdd(&summary[0], (uint32_t)__popcll(mask));
+    atomicMin(&summary[1], (uint32_t)row);
+  }
+}
+template <class P>
+__global__ void __launch_bounds__(256) k_r1cs_check_long(CsrView A, CsrView B, CsrView C, const uint64_t* __restrict__ z, Limbs9 us,
+                                                         const uint64_t* __restrict__ e, uint8_t* __restrict__ status, uint32_t* __restrict__ summary,
+                                                         const uint32_t* __restrict__ long_rows, const uint32_t* __restrict__ long_count) {
+  KG_SERVICE_PRIO();
+  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6), wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  const uint32_t total = *long_count;
+  uint32_t n_bad = 0, first = 0xffffffffu;                // of this wave's rows (the list is in no particular order); lane 0 keeps them
+  for (uint32_t i = wave; i < total; i += nwaves) {      // wave-uniform trip count: the shuffles inside row_dot see full waves
+    const size_t row = long_rows[i];
+    Fp<P> az[1], bz[1], cz[1];
+    row_dot<P, 64, 1>(A.row_ptr, A.col, A.val, row, lane, z, z, az);
+    row_dot<P, 64, 1>(B.row_ptr, B.col, B.val, row, lane, z, z, bz);
+    row_dot<P, 64, 1>(C.row_ptr, C.col, C.val, row, lane, z, z, cz);
+    if (lane == 0) {
+      const bool bad = row_unsat<P>(az[0], bz[0], cz[0], us, e, row);
+      if (status != nullptr) status[row] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
+      if (bad) { ++n_bad; first = min(first, (uint32_t)row); }
+    }
+  }
+  if (lane == 0 && n_bad != 0) {
+    atomicAdd(&summary[0], n_bad);
+    atomicMin(&summary[1], first);
+  }
+}
+
 // ---- splitmix64 streams (oracle/pyoracle.py stream_at, oracle/kg_oracle.c stream_words) ---------------
 __device__ __forceinline__ uint64_t splitmix_next(uint64_t& s) {
   s += 0x9E3779B97F4A7C15ULL;
@@ -457,6 +531,21 @@ int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_
 }
 }  // namespace kg
 
+namespace {
+// u * 2^266 mod p as limbs: ten modular doublings of the ABI form u * 2^256
+Limbs9 scaled(const uint64_t* h_u, bool fr) {
+  Limbs9 out;
+  uint64_t w64[4];
+  if (fr) { HostFr x = HostFr::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
+  else { HostFq x = HostFq::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
+  uint32_t w[8];
+  for (int i = 0; i < 4; ++i) { w[2 * i] = (uint32_t)w64[i]; w[2 * i + 1] = (uint32_t)(w64[i] >> 32); }
+  const Fp<FrParams> lim = limbs_from_words<FrParams>(w);        // the spreading is the same for both fields
+  for (int k = 0; k < 9; ++k) out.l[k] = lim.l[k];
+  return out;
+}
+}  // namespace
+
 extern "C" {
 
 int kg_r1cs_prod(kg_ctx* c, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z, uint64_t* out) {
@@ -481,18 +570,6 @@ int kg_nova_cross_term(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, c
   for (const kg_csr* x : {a, b, cm})
     if (!x->d_row_ptr || !x->d_col || !x->d_val) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
-  // u * 2^266 mod p as limbs: ten modular doublings of the ABI form u * 2^256
-  auto scaled = [&](const uint64_t* h_u, bool fr) {
-    Limbs9 out;
-    uint64_t w64[4];
-    if (fr) { HostFr x = HostFr::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
-    else { HostFq x = HostFq::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
-    uint32_t w[8];
-    for (int i = 0; i < 4; ++i) { w[2 * i] = (uint32_t)w64[i]; w[2 * i + 1] = (uint32_t)(w64[i] >> 32); }
-    const Fp<FrParams> lim = limbs_from_words<FrParams>(w);        // the spreading is the same for both fields
-    for (int k = 0; k < 9; ++k) out.l[k] = lim.l[k];
-    return out;
-  };
   const Limbs9 u1 = scaled(h_u1, field == KG_FR), u2 = scaled(h_u2, field == KG_FR);
   const CsrView A{a->d_row_ptr, a->d_col, a->d_val}, B{b->d_row_ptr, b->d_col, b->d_val}, C{cm->d_row_ptr, cm->d_col, cm->d_val};
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
@@ -509,6 +586,44 @@ int kg_nova_cross_term(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, c
     hipLaunchKernelGGL(k_nova_cross_term_long<FqParams>, dim3(256), dim3(256), 0, c->stream, A, B, C, d_z1, d_z2, u1, u2, d_out, list, count);
   }
   KG_HIP(c, hipGetLastError());
+  return KG_OK;
+}
+
+int kg_r1cs_check(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z, const uint64_t* h_u,
+                  const uint64_t* d_e, uint8_t* d_status, size_t* out_bad, size_t* out_first_bad) {
+  if (!c || (field != KG_FR && field != KG_FQ) || !a || !b || !cm) return KG_ERR_BAD_ARG;
+  if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
+  if (m == 0) {
+    if (out_bad) *out_bad = 0;
+    if (out_first_bad) *out_first_bad = 0;
+    return KG_OK;
+  }
+  if (!d_z) return KG_ERR_BAD_ARG;
+  for (const kg_csr* x : {a, b, cm})
+    if (!x->d_row_ptr || !x->d_col || !x->d_val) return KG_ERR_BAD_ARG;
+  KG_HIP(c, hipSetDevice(c->device));
+  const bool fr = field == KG_FR;
+  const Limbs9 us = scaled(h_u ? h_u : (fr ? HostFrP::ONE : HostFqP::ONE), fr);       // no u: the plain relation, u = 1
+  const CsrView A{a->d_row_ptr, a->d_col, a->d_val}, B{b->d_row_ptr, b->d_col, b->d_val}, C{cm->d_row_ptr, cm->d_col, cm->d_val};
+  KG_TRY(ensure_ws_vec(c, 3 * (m + 16) * 4));             // the work list of long rows (same space as kg_r1cs_prod's); words 2 and 3: the summary
+  uint32_t* count = (uint32_t*)c->ws_vec;
+  uint32_t* summary = count + 2;
+  uint32_t* list = count + 16;
+  hipLaunchKernelGGL(k_r1cs_check_init, dim3(1), dim3(1), 0, c->stream, count, summary, (uint32_t)m);
+  const dim3 grid((unsigned)((m + 255) / 256));
+  if (fr) {
+    hipLaunchKernelGGL(k_r1cs_check<FrParams>, grid, dim3(256), 0, c->stream, A, B, C, m, d_z, us, d_e, d_status, summary, list, count);
+    hipLaunchKernelGGL(k_r1cs_check_long<FrParams>, dim3(256), dim3(256), 0, c->stream, A, B, C, d_z, us, d_e, d_status, summary, list, count);
+  } else {
+    hipLaunchKernelGGL(k_r1cs_check<FqParams>, grid, dim3(256), 0, c->stream, A, B, C, m, d_z, us, d_e, d_status, summary, list, count);
+    hipLaunchKernelGGL(k_r1cs_check_long<FqParams>, dim3(256), dim3(256), 0, c->stream, A, B, C, d_z, us, d_e, d_status, summary, list, count);
+  }
+  KG_HIP(c, hipGetLastError());
+  uint32_t h[2] = {0, 0};
+  KG_HIP(c, hipMemcpyAsync(h, summary, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  KG_HIP(c, hipStreamSynchronize(c->stream));
+  if (out_bad) *out_bad = (size_t)h[0];
+  if (out_first_bad) *out_first_bad = (size_t)h[1];
   return KG_OK;
 }
 

@@ -32,4 +32,27 @@ KG_HD F cross_term_row(const F& az1, const F& az2, const F& bz1, const F& bz2, c
   return vred(norm(sub<8, 1>(norm(sub<4, 1>(had, c1)), c2)));
 }
 
+// The residual of one constraint row of the (relaxed) R1CS relation (nova/src/relaxed_r1cs.rs:81-114 is_sat_relaxed; with u = 1, E = 0
+// zkstd/src/r1cs.rs:62-77 is_sat):   (A z)_i (B z)_i - u (C z)_i - E_i,   in the ABI domain (times 2^256).
+// az, bz, cz: row sums as dot_step / dot_merge leave them (x * 2^251, normalised, below 1.06p; zero() for an empty row).
+// us: u * 2^266, normalised, below 2p (the kernel gets the canonical value from ten host-side doublings of the ABI form; the Montgomery
+//     one doubled ten times when the caller has no u).  e_raw: E_i as it lies in memory (the ABI words as limbs: any 256-bit value,
+//     below 5.4p, limbs normalised by the unpacking); zero() when the caller has no E.  had_const: 2^276 (P::C_XT_HAD).
+// Bounds: the two products are normalised and below 1.01p, so 4p dominates the first subtrahend and 8p the raw word (sub<4, 1>, sub<8, 1>:
+// limbs up to 2^29 - 1, top limb below the fat constant's); the lazy value had + 4p - c + 8p - e lies in (5.5p, 13.1p), its top limb
+// below 2^27 after the carries, which is what vred accepts.  Result: normalised, below 1.06p.
+template <class F>
+KG_HD F sat_residual_row(const F& az, const F& bz, const F& cz, const F& us, const F& e_raw, const F& had_const) {
+  const F had = mul(mul(az, bz), had_const);
+  const F cu = mul(cz, us);
+  return vred(norm(sub<8, 1>(norm(sub<4, 1>(had, cu)), e_raw)));
+}
+// Is a residual as sat_residual_row leaves it zero in the field?  The value is the canonical residue or that plus p (vred's quotient
+// estimate may be one short), never more: a row that holds arrives as 0 or as p.  BOTH occur -- the lazy value of a satisfied row is k p
+// with 6 <= k <= 13 and vred takes off k p or (k - 1) p, decided by the top limb alone (a row with no entries and E = 0 is the lazy
+// value 12p: limbs of the two fat constants, nothing else).  So the test compares with both representatives, which is what canonicalising (reduce_2p: p -> 0) and
+// comparing with zero comes to, without the subtraction.  Inputs outside [0, 2p) are a bound violation (FpChecked aborts on them).
+template <class F>
+KG_HD bool is_zero_mod_p(const F& residual) { return is_zero_2p(residual); }
+
 }  // namespace kg

@@ -18,6 +18,7 @@ KG_FR, KG_FQ = 0, 1
 KG_G1, KG_GRUMPKIN, KG_G2 = 0, 1, 2
 KG_CHECK_CURVE, KG_CHECK_SUBGROUP = 1, 2                                # `checks` mask of kg_points_check
 KG_PT_NON_CANONICAL, KG_PT_OFF_CURVE, KG_PT_NOT_IN_SUBGROUP = 1, 2, 4   # per-point status bits
+KG_ROW_UNSAT = 1                                                        # per-row status of kg_r1cs_check
 CRS_CHECK_MEMBERS = ("h", "l", "a", "b_g1", "b_g2", "alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")
 OPS = {"add": 0, "sub": 1, "mul": 2, "square": 3, "neg": 4, "double": 5, "invert": 6, "from_mont": 7, "to_mont": 8}
 EXPORTS = [
@@ -30,7 +31,7 @@ EXPORTS = [
     "kg_sharded_key_len", "kg_sharded_key_commit", "kg_r1cs_prod", "kg_nova_cross_term", "kg_ctx_set_inputs_complete", "kg_bases_precompute", "kg_msm_table_window", "kg_groth16_prove_r1cs_bn254", "kg_groth16_prove_r1cs_begin", "kg_groth16_prove_sharded", "kg_ntt_plan",
     "kg_msm_host_scalars", "kg_commit_host_scalars", "kg_tuning_describe", "kg_mem_info", "kg_groth16_setup_bn254", "kg_experiments_built", "kg_msm_host_slices",
     "kg_msm_set_small", "kg_ctx_worker_threads", "kg_ctx_queue_placement2", "kg_ctx_trim",
-    "kg_points_check", "kg_groth16_crs_check",
+    "kg_points_check", "kg_groth16_crs_check", "kg_r1cs_check",
 ]
 
 
@@ -92,6 +93,9 @@ def load():
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         _lib.kg_groth16_crs_check.restype = C.c_int
         _lib.kg_groth16_crs_check.argtypes = [C.c_void_p, C.POINTER(Groth16Crs), C.c_int, C.POINTER(C.c_size_t)]
+        _lib.kg_r1cs_check.restype = C.c_int
+        _lib.kg_r1cs_check.argtypes = [C.c_void_p, C.c_int, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     return _lib
 
 
@@ -383,6 +387,21 @@ class Context:
         u2 = np.ascontiguousarray(u2, dtype=np.uint64)
         self._chk(self._lib.kg_nova_cross_term(self._h, field, C.byref(ca), C.byref(cb), C.byref(cc), C.c_size_t(m), _vp(z1), _vp(z2),
                                                u1.ctypes.data_as(C.c_void_p), u2.ctypes.data_as(C.c_void_p), _vp(out)), "kg_nova_cross_term")
+
+    def r1cs_check(self, field: int, a, b, c, m: int, z: int, u=None, e: int = 0, status: int = 0) -> tuple[int, int]:
+        """kg_r1cs_check: (number of rows i with (A z)_i (B z)_i != u (C z)_i + E_i, smallest such row or m).  a, b, c: (row_ptr, col, val)
+        device pointers; z, e, status: device pointers (e = 0: E = 0; status = 0: no status bytes); u: one element on the host (None: u = 1).
+        Runs behind what the context's stream holds; blocks."""
+        mk = lambda t: Csr(_vp(t[0]), _vp(t[1]), _vp(t[2]))
+        ca, cb, cc = mk(a), mk(b), mk(c)
+        hu = None
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.uint64).reshape(4)
+            hu = u.ctypes.data_as(C.c_void_p)
+        bad, first = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self._lib.kg_r1cs_check(self._h, int(field), C.byref(ca), C.byref(cb), C.byref(cc), C.c_size_t(m), _vp(z), hu, _vp(e), _vp(status),
+                                          C.byref(bad), C.byref(first)), "kg_r1cs_check")
+        return int(bad.value), int(first.value)
 
     def fixed_base_mul(self, curve: int, k: int, n: int, out_xy: int, out_inf: int):
         self._chk(self._lib.kg_fixed_base_mul(self._h, curve, _vp(k), C.c_size_t(n), _vp(out_xy), _vp(out_inf)), "kg_fixed_base_mul")

@@ -84,6 +84,9 @@ pub const KG_PT_OFF_CURVE: i32 = 2;
 /// G2 only: `[r]P != O`
 pub const KG_PT_NOT_IN_SUBGROUP: i32 = 4;
 
+/// kg_r1cs_check: the per-row status of a constraint that does not hold
+pub const KG_ROW_UNSAT: i32 = 1;
+
 // kg_field_op
 pub const KG_OP_ADD: i32 = 0;
 pub const KG_OP_SUB: i32 = 1;

@@ -61,6 +61,60 @@ pub fn cross_term<F: PrimeField + 'static>(a: &SparseMatrix<F>, b: &SparseMatrix
     Some(t)
 }
 
+/// `R1csShape::is_sat_relaxed` (nova/src/relaxed_r1cs.rs:81-114): AZ o BZ = u CZ + E row by row through `kg_r1cs_check`, on the
+/// same resident shape as `cross_term`.  Returns (rows that do not hold, the first of them or `m`); `None` (no device, an unserved
+/// field, any non-zero status) lets the caller's CPU body run.  The reference asserts it around every fold (prover.rs:163-165).
+#[allow(clippy::too_many_arguments)]
+pub fn is_sat_relaxed<F: PrimeField + 'static>(a: &SparseMatrix<F>, b: &SparseMatrix<F>, c: &SparseMatrix<F>, m: u64, l: usize, z: &[F], u: &F,
+                                               e: &[F]) -> Option<(usize, usize)> {
+    if e.len() != m as usize {
+        return None;
+    }
+    check(a, b, c, m, l, z, Some(u), Some(e))
+}
+
+/// The constraint half of `R1csShape::is_sat` (relaxed_r1cs.rs:117-146) and `R1cs::is_sat` (zkstd/src/r1cs.rs:62-77): AZ o BZ = CZ
+/// (u = 1, E = 0; nothing is uploaded for either).  The commitment half stays with the caller (`pedersen::commit` and `==`).
+pub fn is_sat<F: PrimeField + 'static>(a: &SparseMatrix<F>, b: &SparseMatrix<F>, c: &SparseMatrix<F>, m: u64, l: usize, z: &[F]) -> Option<(usize, usize)> {
+    check(a, b, c, m, l, z, None, None)
+}
+
+#[allow(clippy::too_many_arguments)]
+fn check<F: PrimeField + 'static>(a: &SparseMatrix<F>, b: &SparseMatrix<F>, c: &SparseMatrix<F>, m: u64, l: usize, z: &[F], u: Option<&F>,
+                                  e: Option<&[F]>) -> Option<(usize, usize)> {
+    let (_, field) = scalar_words(z)?;
+    if m == 0 {
+        return Some((0, 0));
+    }
+    let ctxs = contexts()?;
+    let ctx = ctxs.lock(0)?;                                   // the shapes are resident on GPU 0
+    let ctx = &*ctx;
+    let print = content_hash([a, b, c], l)?;
+    let mut guard = SHAPES.lock().ok()?;
+    let shapes = guard.get_or_insert_with(HashMap::new);
+    let key = (m as usize, l, field);
+    if shapes.get(&key).map(|s| s.fingerprint != print).unwrap_or(true) {
+        shapes.insert(key, ResidentShape::build(ctx, a, b, c, l, print)?);
+    }
+    let shape = shapes.get(&key)?;
+    if !shape.covers(m as usize, z.len()) {
+        return None;
+    }
+    let words = |s: &[F]| unsafe { core::slice::from_raw_parts(s.as_ptr() as *const u64, 4 * s.len()) };
+    let dz = DeviceBuf::from_words(ctx, words(z)).ok()?;
+    let de = match e {
+        Some(e) => Some(DeviceBuf::from_words(ctx, words(e)).ok()?),
+        None => None,
+    };
+    let (ca, cb, cc) = (shape.m[0].csr(), shape.m[1].csr(), shape.m[2].csr());
+    let (mut bad, mut first) = (0usize, 0usize);
+    let rc = unsafe {
+        sys::kg_r1cs_check(ctx.raw(), field, &ca, &cb, &cc, m as usize, dz.as_u64(), u.map_or(core::ptr::null(), |u| u as *const F as *const u64),
+                           de.as_ref().map_or(core::ptr::null(), |d| d.as_u64() as *const u64), core::ptr::null_mut(), &mut bad, &mut first)
+    };
+    if rc == sys::KG_OK { Some((bad, first)) } else { None }
+}
+
 /// shortest vector whose fold goes to the device: below this the two PCIe trips cost more than the host's multiply-adds
 const AXPY_MIN_LEN: usize = 1 << 14;
 
