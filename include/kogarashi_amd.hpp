@@ -216,8 +216,29 @@ class Fft {
     d.download(buf.data());
     return buf;
   }
+  // Many polynomials of this size in ONE call (kg_ntt_bn254_fr_batch: one launch per plan step for the whole batch): every row is
+  // zero-padded to 2^k elements like run(), the rows travel as one flat array with stride 2^k and come back transformed.
+  std::vector<std::vector<Fe>> batch(const std::vector<std::vector<Fe>>& vs, int inverse = 0, int coset = 0) const {
+    return run_batch(vs, [&](uint64_t* d) { return c_.check(kg_ntt_bn254_fr_batch(c_.raw(), d, k_, vs.size(), n_, inverse, coset), "kg_ntt_bn254_fr_batch"); });
+  }
+  std::vector<std::vector<Fe>> divide_by_z_on_coset_batch(const std::vector<std::vector<Fe>>& vs) const {
+    return run_batch(vs, [&](uint64_t* d) { return c_.check(kg_fr_divide_by_z_on_coset_batch(c_.raw(), d, k_, vs.size(), n_), "kg_fr_divide_by_z_on_coset_batch"); });
+  }
 
  private:
+  template <class Call>
+  std::vector<std::vector<Fe>> run_batch(const std::vector<std::vector<Fe>>& vs, Call&& call) const {
+    std::vector<std::vector<Fe>> out(vs.size());
+    if (vs.empty()) return out;
+    std::vector<Fe> flat(vs.size() * n_, Fe{0, 0, 0, 0});
+    for (size_t b = 0; b < vs.size(); ++b)
+      for (size_t i = 0; i < vs[b].size() && i < n_; ++i) flat[b * n_ + i] = vs[b][i];
+    DeviceBuffer d(c_, flat.data(), flat.size() * 32);
+    call(d.as<uint64_t>());
+    d.download(flat.data());
+    for (size_t b = 0; b < vs.size(); ++b) out[b].assign(flat.begin() + b * n_, flat.begin() + (b + 1) * n_);
+    return out;
+  }
   std::vector<Fe> padded(const std::vector<Fe>& v) const {
     std::vector<Fe> buf(n_, Fe{0, 0, 0, 0});
     for (size_t i = 0; i < v.size() && i < n_; ++i) buf[i] = v[i];

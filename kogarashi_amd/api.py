@@ -98,6 +98,32 @@ class Fft:
         self.ctx.divide_by_z_on_coset(d.ptr, self.k)
         return d.numpy()
 
+    def _rows(self, vs):
+        """B polynomials (a (B, <= n, 4) array or a list of (<= n, 4) arrays) -> a zero-padded (B, n, 4) array, each row like _run"""
+        buf = np.zeros((len(vs), self.n, 4), dtype=np.uint64)
+        for b, v in enumerate(vs):
+            v = np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4)
+            buf[b, : min(len(v), self.n)] = v[: self.n]
+        return buf
+
+    def batch(self, vs, inverse=False, coset=False):
+        """every row of vs through one transform (dft / idft / coset_dft / coset_idft by the two flags) in a single call
+        (kg_ntt_bn254_fr_batch): (B, <= n, 4) in, (B, n, 4) out"""
+        buf = self._rows(vs)
+        if len(buf) == 0:
+            return buf
+        d = self.ctx.upload(buf.reshape(-1, 4))
+        self.ctx.ntt_batch(d.ptr, self.k, len(buf), self.n, inverse, coset)
+        return d.numpy().reshape(len(buf), self.n, 4)
+
+    def divide_by_z_on_coset_batch(self, vs):
+        buf = self._rows(vs)
+        if len(buf) == 0:
+            return buf
+        d = self.ctx.upload(buf.reshape(-1, 4))
+        self.ctx.divide_by_z_on_coset_batch(d.ptr, self.k, len(buf), self.n)
+        return d.numpy().reshape(len(buf), self.n, 4)
+
 
 class PedersenCommitment:
     """nova::PedersenCommitment<C>: commit(m) = affine(sum_i g[i] * m[i]) over min(len) pairs.

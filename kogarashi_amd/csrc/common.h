@@ -312,6 +312,10 @@ int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_
 // ntt.hip
 int ntt_prepare(kg_ctx* ctx, uint32_t log_n, int inverse);
 int ntt_enqueue(kg_ctx* ctx, hipStream_t st, uint64_t* tmp, uint64_t* d_data, uint32_t log_n, int inverse, int coset);
+// the context's cached tables of a (log_n, inverse) pair, built on the main stream at first use (ntt_batch.hip launches with them);
+// zinv (may be null): where the pair's (7^n - 1)^-1 lives
+struct NttTables;   // ntt_tile.h
+int ntt_tables(kg_ctx* ctx, uint32_t log_n, int inverse, NttTables* out, const uint32_t** zinv);
 // ordered: the caller has already put the scalar queue (ctx->sort_stream, see scalar_queue()) behind the producer of
 // d_scalars; otherwise msm_sort orders it after everything enqueued on the main queue so far (stream semantics), or not
 // at all when the context's inputs are declared complete (kg_ctx_set_inputs_complete)

@@ -249,6 +249,14 @@ int ntt_prepare(kg_ctx* ctx, uint32_t log_n, int inverse) {
   return get_tables(ctx, log_n, inverse ? 1 : 0, &T);
 }
 
+int ntt_tables(kg_ctx* ctx, uint32_t log_n, int inverse, NttTables* out, const uint32_t** zinv) {
+  kg_tw_cache* T;
+  KG_TRY(get_tables(ctx, log_n, inverse ? 1 : 0, &T));
+  *out = NttTables{T->small, T->lo, T->hi, T->cos_lo, T->cos_hi, T->direct[0], T->direct[1], T->lo_bits};
+  if (zinv) *zinv = T->zinv;
+  return KG_OK;
+}
+
 // Enqueue one transform on `st`; tmp: scratch of n elements private to this call (unused when log_n <= 11).
 int ntt_enqueue(kg_ctx* ctx, hipStream_t st, uint64_t* tmp, uint64_t* d_data, uint32_t log_n, int inverse, int coset) {
   inverse = inverse ? 1 : 0;

@@ -32,6 +32,7 @@ EXPORTS = [
     "kg_msm_host_scalars", "kg_commit_host_scalars", "kg_tuning_describe", "kg_mem_info", "kg_groth16_setup_bn254", "kg_experiments_built", "kg_msm_host_slices",
     "kg_msm_set_small", "kg_ctx_worker_threads", "kg_ctx_queue_placement2", "kg_ctx_trim",
     "kg_points_check", "kg_groth16_crs_check", "kg_r1cs_check",
+    "kg_ntt_bn254_fr_batch", "kg_fr_divide_by_z_on_coset_batch", "kg_ntt_batch_plan",
 ]
 
 
@@ -96,6 +97,12 @@ def load():
         _lib.kg_r1cs_check.restype = C.c_int
         _lib.kg_r1cs_check.argtypes = [C.c_void_p, C.c_int, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_size_t, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        _lib.kg_ntt_bn254_fr_batch.restype = C.c_int
+        _lib.kg_ntt_bn254_fr_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, C.c_int]
+        _lib.kg_fr_divide_by_z_on_coset_batch.restype = C.c_int
+        _lib.kg_fr_divide_by_z_on_coset_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t]
+        _lib.kg_ntt_batch_plan.restype = C.c_int
+        _lib.kg_ntt_batch_plan.argtypes = [C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t)]
     return _lib
 
 
@@ -119,6 +126,14 @@ def ntt_plan(log_n: int) -> list[tuple[int, int]]:
     m, t = (C.c_uint32 * 3)(), (C.c_uint32 * 3)()
     s = int(load().kg_ntt_plan(C.c_uint32(log_n), m, t))
     return [(int(m[i]), int(t[i])) for i in range(s)]
+
+
+def ntt_batch_plan(log_n: int, count: int) -> tuple[int, int]:
+    """kg_ntt_batch_plan: (launch groups a batch of `count` transforms of 2^log_n elements is cut into, most transforms one group
+    carries); (0, 0) for log_n outside 1..28, 0 groups for count == 0 (no device needed)"""
+    per = C.c_size_t(0)
+    groups = int(load().kg_ntt_batch_plan(C.c_uint32(log_n), C.c_size_t(count), C.byref(per)))
+    return groups, int(per.value)
 
 
 def tuning_table() -> list[dict]:
@@ -258,6 +273,15 @@ class Context:
 
     def ntt(self, data: int, log_n: int, inverse: bool, coset: bool):
         self._chk(self._lib.kg_ntt_bn254_fr(self._h, _vp(data), C.c_uint32(log_n), int(bool(inverse)), int(bool(coset))), "kg_ntt_bn254_fr")
+
+    def ntt_batch(self, data: int, log_n: int, count: int, stride: int, inverse: bool, coset: bool):
+        """count transforms of 2^log_n elements in one call; transform b starts at element b * stride of data (stride >= 2^log_n)"""
+        self._chk(self._lib.kg_ntt_bn254_fr_batch(self._h, _vp(data), C.c_uint32(log_n), C.c_size_t(count), C.c_size_t(stride), int(bool(inverse)),
+                                                  int(bool(coset))), "kg_ntt_bn254_fr_batch")
+
+    def divide_by_z_on_coset_batch(self, data: int, log_n: int, count: int, stride: int):
+        self._chk(self._lib.kg_fr_divide_by_z_on_coset_batch(self._h, _vp(data), C.c_uint32(log_n), C.c_size_t(count), C.c_size_t(stride)),
+                  "kg_fr_divide_by_z_on_coset_batch")
 
     def divide_by_z_on_coset(self, data: int, log_n: int):
         self._chk(self._lib.kg_fr_divide_by_z_on_coset(self._h, _vp(data), C.c_uint32(log_n)), "kg_fr_divide_by_z_on_coset")
