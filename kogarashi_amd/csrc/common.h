@@ -208,6 +208,55 @@ void prof_reset(kg_ctx* c);
 // ---- device-side layouts ------------------------------------------------------------------------
 // A field element in the ABI: 8 x u32 words (4 x u64 LE).  Loaded/stored as two 16-byte vectors.
 struct alignas(16) Words8 { uint32_t w[8]; };
+inline Words8 words8(const uint64_t h[4]) {
+  Words8 r;
+  for (int i = 0; i < 4; ++i) { r.w[2 * i] = (uint32_t)h[i]; r.w[2 * i + 1] = (uint32_t)(h[i] >> 32); }
+  return r;
+}
+
+// The work space of the sparse-row kernels (vec.hip), in 32-bit words.  kg_ctx::ws_vec holds REGIONS of them side by side: the prover runs
+// three products at once, every other caller uses region 0.
+struct RowWs {
+  static constexpr int REGIONS = 3;
+  static constexpr size_t words(size_t m) { return m + 16; }                       // of one region for m rows
+  static constexpr size_t bytes(size_t m) { return REGIONS * words(m) * 4; }       // what ensure_ws_vec is asked for
+  uint32_t* count;      // [0]: rows on the list's front (a wave each), [1]: rows on its back (kg_r1cs_prod's huge rows, a workgroup each)
+  uint32_t* summary;    // kg_r1cs_check: bad rows | first bad row (BadSummary)
+  uint32_t* list;       // the work list of long rows: up to m entries
+  RowWs(void* ws_vec, size_t m, int region = 0) : count((uint32_t*)ws_vec + region * words(m)), summary(count + 2), list(count + 16) {}
+};
+
+// ---- "how many items are bad, and which is the first": two words {count, lowest index} of type W in device memory -------------------
+// (kg_points_check: 64-bit words, n up to 2^37; kg_r1cs_check: 32-bit words inside RowWs, rows below 2^32).  k_summary_init sets them to
+// (0, n) on the stream before the kernels that fold into them -- and clears one more 32-bit word when given one (the check's long-row
+// counter) --, summary_read brings them back: it blocks.
+template <class W>
+static __global__ void k_summary_init(W* summary, W n, uint32_t* also_clear) {
+  summary[0] = 0;
+  summary[1] = n;
+  if (also_clear) *also_clear = 0;
+}
+// ONE lane speaks for n_bad items whose lowest index is `first`: one atomicAdd, one atomicMin
+template <class W>
+__device__ __forceinline__ void summary_add(W* summary, W n_bad, W first) {
+  atomicAdd(&summary[0], n_bad);
+  atomicMin(&summary[1], first);
+}
+// every lane of a wave with its own item (ascending with the lane): one ballot, and the lowest bad lane speaks for the wave
+template <class W>
+__device__ __forceinline__ void summary_fold(W* summary, bool bad, W item) {
+  const unsigned long long mask = __ballot(bad);
+  if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) summary_add(summary, (W)__popcll(mask), item);
+}
+template <class W>
+int summary_read(kg_ctx* c, const W* summary, size_t* out_bad, size_t* out_first_bad) {
+  W h[2] = {0, 0};
+  KG_HIP(c, hipMemcpyAsync(h, summary, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  KG_HIP(c, hipStreamSynchronize(c->stream));
+  if (out_bad) *out_bad = (size_t)h[0];
+  if (out_first_bad) *out_first_bad = (size_t)h[1];
+  return KG_OK;
+}
 
 __device__ __forceinline__ void load_words(const uint64_t* base, size_t elem, uint32_t w[8]) {
   const uint4* p = reinterpret_cast<const uint4*>(base) + 2 * elem;
@@ -306,9 +355,9 @@ struct MsmSorted {
   // real window count, an entry's index field is (window << merged_shift) | scalar index
   int merged_shift = 0, windows = 0;
 };
-// vec.hip: CSR matrix-vector product on a given queue; scratch = (m + 16) words (kg_ctx::ws_vec holds three such regions)
+// vec.hip: CSR matrix-vector product on a given queue; ws: a region of kg_ctx::ws_vec that nothing else uses meanwhile
 int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
-                      const uint64_t* z, uint64_t* out, uint32_t* scratch);
+                      const uint64_t* z, uint64_t* out, const RowWs& ws);
 // ntt.hip
 int ntt_prepare(kg_ctx* ctx, uint32_t log_n, int inverse);
 int ntt_enqueue(kg_ctx* ctx, hipStream_t st, uint64_t* tmp, uint64_t* d_data, uint32_t log_n, int inverse, int coset);

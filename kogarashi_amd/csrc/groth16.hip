@@ -441,7 +441,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
   if (need_z && m_l_1) KG_HIP(ctx, hipMemcpyAsync(Z + 4 * l, d_w, m_l_1 * 32, hipMemcpyDeviceToDevice, sq));
   if (mats && do_h) {
     if (m >= ((size_t)1 << 32)) return set_err(ctx, KG_ERR_BAD_ARG, "more than 2^32 constraints");
-    KG_TRY(ensure_ws_vec(ctx, 3 * (m + 16) * 4));
+    KG_TRY(ensure_ws_vec(ctx, RowWs::bytes(m)));
     KG_HIP(ctx, hipEventRecord(ctx->ev_order, sq));       // z is complete: the matrix-vector products of the chains wait for it
   }
   MsmSorted Sz;
@@ -500,6 +500,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
   // the chains share the two reduction queues (queues of their own: 3.31 ms per proof against 2.83 -- transforms and halving
   // levels do not fit the chip together with an accumulation anyway, and in one queue they do not fight each other for it)
   hipStream_t lanes[3] = {ctx->side_stream, ctx->side2_stream, ctx->side_stream};
+  static_assert(RowWs::REGIONS == 3, "one work-space region per chain: the three products run at once");
   for (int v = 0; v < 3 && rc == KG_OK && do_h; ++v) {    // prepare_fft zero padding, then idft + coset_dft
     hipStream_t sv = lanes[v];
     uint64_t* tmp = TMP + (size_t)v * 4 * n;
@@ -507,7 +508,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
     if (mats) {                                           // row v of cs.evaluate(): M_v z, z as the scalar queue assembled it
       hip_rc(hipStreamWaitEvent(sv, ctx->ev_order, 0), "hipStreamWaitEvent(z)");
       if (rc == KG_OK) rc = r1cs_prod_enqueue(ctx, sv, KG_FR, mats[v]->d_row_ptr, mats[v]->d_col, mats[v]->d_val, m, Z, dst[v],
-                                              (uint32_t*)ctx->ws_vec + (size_t)v * (m + 16));
+                                              RowWs(ctx->ws_vec, m, v));
     } else
       hip_rc(hipMemcpyAsync(dst[v], src[v], m * 32, hipMemcpyDeviceToDevice, sv), "hipMemcpyAsync(evaluations)");
     if (n > m) hip_rc(hipMemsetAsync(dst[v] + 4 * m, 0, (n - m) * 32, sv), "hipMemsetAsync(padding)");
@@ -546,9 +547,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
     HostFr z = seven;
     for (uint32_t i = 0; i < k; ++i) z = sqr(z);
     z = inv(sub<4, 1>(z, HostFr::one()));                 // z_on_coset().invert() (fft.rs:141-151)
-    Words8 zw;
-    for (int i = 0; i < 4; ++i) { zw.w[2 * i] = (uint32_t)z.v[i]; zw.w[2 * i + 1] = (uint32_t)(z.v[i] >> 32); }
-    hipLaunchKernelGGL(k_qap_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hq, A, B, C, n, zw);
+    hipLaunchKernelGGL(k_qap_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hq, A, B, C, n, words8(z.v));
     hip_rc(hipGetLastError(), "k_qap_combine launch");
     if (rc == KG_OK) rc = ntt_enqueue(ctx, hq, TMP, A, k, 1, 1);             // coset_idft (prover.rs:47)
   };

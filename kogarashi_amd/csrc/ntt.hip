@@ -92,33 +92,12 @@ __global__ void __launch_bounds__(64) k_build_direct(uint32_t log_n, int inverse
   st_tw(tab, e, pow_u64(root_of(log_n, inverse), r * c * mult));
 }
 
-#ifndef KG_NTT_WAVES
-#define KG_NTT_WAVES 4
-#endif
 // One tile per workgroup; see ntt_tile.h.  NT = tile / 4 threads (one radix-4 group per lane and pass).
 template <int LOG_M, int LOG_TC, bool ROW>
 __global__ void __launch_bounds__((NttTile<Fr, LOG_M, LOG_TC, ROW>::NT)) __attribute__((amdgpu_waves_per_eu(KG_NTT_WAVES))) k_ntt_tile(NttStepArgs A) {   // <= 128 VGPRs: LDS admits four waves per SIMD
   KG_SERVICE_PRIO();
-  using T = NttTile<Fr, LOG_M, LOG_TC, ROW>;
   extern __shared__ uint32_t lds[];
-  uint32_t tile = blockIdx.x;
-  if (A.tile_shift) tile = ((tile & 7u) << A.tile_shift) | (tile >> 3);     // workgroup i runs on XCD i mod 8: neighbouring tiles share an L2
-  const T t{A, tile};
-  const LdsPlanes<T::ELEMS> st{lds};
-  t.first(threadIdx.x, st);
-  if constexpr (!T::SINGLE) {
-#ifdef KG_NTT_EXP_NOBAR      // phase-off experiment (tools/dbg): no workgroup barriers (results are wrong, timing only)
-    const auto full = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-#else
-    const auto full = [] { __syncthreads(); };
-#endif
-    // between two wave-private passes: the wave's own LDS writes are ordered before its reads by the in-order LDS queue; the
-    // fence keeps the compiler from moving them across the boundary
-    const auto wave = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    t.after_first(full, wave);
-    t.template mids<T::G0>(threadIdx.x, st, full, wave);
-    t.last(threadIdx.x, st);
-  }
+  ntt_tile_run<NttTile<Fr, LOG_M, LOG_TC, ROW>>(A, lds);
 }
 
 // data[i] *= c   (c: one internal-form constant in device memory)
@@ -140,13 +119,6 @@ __global__ void k_build_zinv(uint32_t log_n, uint32_t* __restrict__ out) {
   st_tw(out, 0, inv(norm(sub<4, 1>(g, Fr::one()))));
 }
 
-int plan_tile_env() {        // KG_NTT_TILE=10..12: log2 of the tile size (experiments)
-  return tuning().ntt_tile;
-}
-int plan_steps_env() {       // KG_NTT_STEPS=3: three-step plans from 2^18 up; 2: two steps up to 2^22 (experiments; default: ntt_plan's automatic rule)
-  return tuning().ntt_steps;
-}
-
 void free_tables(kg_tw_cache* t) {
   hipFree(t->small); hipFree(t->lo); hipFree(t->hi); hipFree(t->cos_lo); hipFree(t->cos_hi); hipFree(t->zinv);
   hipFree(t->direct[0]); hipFree(t->direct[1]);
@@ -161,7 +133,7 @@ int get_tables(kg_ctx* ctx, uint32_t log_n, int inverse, kg_tw_cache** out) {
   t->lo_bits = (log_n + 1) / 2;
   const uint32_t n_lo = 1u << t->lo_bits, n_hi = 1u << (log_n - t->lo_bits);
   NttStepDesc d[3];
-  const int nsteps = ntt_plan(log_n, plan_steps_env(), d, plan_tile_env());
+  const int nsteps = ntt_plan(log_n, tuning().ntt_steps, d, tuning().ntt_tile);
   // direct inter-step tables: step A w_n^(i1 * c), c < n / n1 (n entries; kept while it is worth its memory: 36 MB at 2^20,
   // 151 MB at 2^22), step B of a three-step plan w_n^(n1 * i2 * j3) (n2 * n3 entries)
   const size_t cnt_a = (nsteps >= 2 && log_n <= direct_a_max_log()) ? (size_t)1 << log_n : 0;
@@ -203,30 +175,17 @@ int get_tables(kg_ctx* ctx, uint32_t log_n, int inverse, kg_tw_cache** out) {
 
 // ---- dispatch: one kernel instantiation per tile shape ntt_plan can ask for ------------------------------------
 template <int LOG_M, int LOG_TC, bool ROW>
-int launch_tile(kg_ctx* ctx, hipStream_t st, const NttStepArgs& a, uint32_t ntiles) {
+int launch_tile(NttShape<LOG_M, LOG_TC, ROW>, kg_ctx* ctx, hipStream_t st, const NttStepArgs& a, uint32_t ntiles) {
   using T = NttTile<Fr, LOG_M, LOG_TC, ROW>;
-  const size_t lds_bytes = T::SINGLE ? 0 : (size_t)T::ELEMS * 36;
-  if (lds_bytes > 48 * 1024)               // more than the default dynamic LDS limit needs the attribute (per device: set at every launch)
-    KG_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_tile<LOG_M, LOG_TC, ROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((k_ntt_tile<LOG_M, LOG_TC, ROW>), dim3(ntiles), dim3(T::NT), lds_bytes, st, a);
+  if (T::LDS_BYTES > 48 * 1024)            // more than the default dynamic LDS limit needs the attribute (per device: set at every launch)
+    KG_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_tile<LOG_M, LOG_TC, ROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::LDS_BYTES));
+  hipLaunchKernelGGL((k_ntt_tile<LOG_M, LOG_TC, ROW>), dim3(ntiles), dim3(T::NT), T::LDS_BYTES, st, a);
   return KG_OK;
 }
 int launch_step(kg_ctx* ctx, hipStream_t st, const NttStepDesc& d, const NttStepArgs& a, uint32_t ntiles) {
-  const int key = d.log_m * 16 + d.log_tc;
-  if (!d.row) {
-    switch (key) {
-#define X(m, tc) case (m) * 16 + (tc): return launch_tile<m, tc, false>(ctx, st, a, ntiles);
-      KG_NTT_SHAPES(X) KG_NTT_SHAPES_COL_ONLY(X)
-#undef X
-    }
-  } else {
-    switch (key) {
-#define X(m, tc) case (m) * 16 + (tc): return launch_tile<m, tc, true>(ctx, st, a, ntiles);
-      KG_NTT_SHAPES(X) KG_NTT_SHAPES_ROW_ONLY(X)
-#undef X
-    }
-  }
-  return set_err(ctx, KG_ERR_UNSUPPORTED, "ntt tile shape not instantiated");
+  int rc = KG_OK;
+  if (!ntt_for_shape(d, [&](auto shape) { rc = launch_tile(shape, ctx, st, a, ntiles); })) return set_err(ctx, KG_ERR_UNSUPPORTED, "ntt tile shape not instantiated");
+  return rc;
 }
 
 }  // namespace
@@ -237,10 +196,6 @@ void tw_cache_free(kg_ctx* c) {
   c->tw.clear();
 }
 }  // namespace kg
-
-extern "C" {
-
-}  // extern "C"
 
 namespace kg {
 // Build (or find) the twiddle tables of a transform size on the context's main stream.
@@ -260,13 +215,12 @@ int ntt_tables(kg_ctx* ctx, uint32_t log_n, int inverse, NttTables* out, const u
 // Enqueue one transform on `st`; tmp: scratch of n elements private to this call (unused when log_n <= 11).
 int ntt_enqueue(kg_ctx* ctx, hipStream_t st, uint64_t* tmp, uint64_t* d_data, uint32_t log_n, int inverse, int coset) {
   inverse = inverse ? 1 : 0;
-  kg_tw_cache* T;
-  KG_TRY(get_tables(ctx, log_n, inverse, &T));
+  NttTables tabs;
+  KG_TRY(ntt_tables(ctx, log_n, inverse, &tabs, nullptr));
   NttStepDesc d[3];
-  const int nsteps = ntt_plan(log_n, plan_steps_env(), d, plan_tile_env());
+  const int nsteps = ntt_plan(log_n, tuning().ntt_steps, d, tuning().ntt_tile);
   if (nsteps > 1 && !tmp) return set_err(ctx, KG_ERR_BAD_ARG, "ntt scratch missing");
 
-  const NttTables tabs{T->small, T->lo, T->hi, T->cos_lo, T->cos_hi, T->direct[0], T->direct[1], T->lo_bits};
   PhaseScope ph(ctx, "ntt", st);
   for (int i = 0; i < nsteps; ++i) {
     NttStepArgs a;
@@ -297,7 +251,7 @@ int kg_ntt_bn254_fr(kg_ctx* ctx, uint64_t* d_data, uint32_t log_n, int inverse, 
 int kg_ntt_plan(uint32_t log_n, uint32_t* log_m, uint32_t* log_tile) {
   if (log_n < 1 || log_n > 28 || !log_m || !log_tile) return 0;
   NttStepDesc d[3];
-  const int s = ntt_plan(log_n, plan_steps_env(), d, plan_tile_env());
+  const int s = ntt_plan(log_n, tuning().ntt_steps, d, tuning().ntt_tile);
   for (int i = 0; i < 3; ++i) {
     log_m[i] = i < s ? (uint32_t)d[i].log_m : 0u;
     log_tile[i] = i < s ? (uint32_t)(d[i].log_m + d[i].log_tc) : 0u;
@@ -309,10 +263,11 @@ int kg_fr_divide_by_z_on_coset(kg_ctx* ctx, uint64_t* d_data, uint32_t log_n) {
   // fft.rs:150-154: every evaluation * (7^n - 1)^-1
   if (!ctx || !d_data || log_n < 1 || log_n > 28) return KG_ERR_BAD_ARG;
   KG_HIP(ctx, hipSetDevice(ctx->device));
-  kg_tw_cache* T;
-  KG_TRY(get_tables(ctx, log_n, 0, &T));
+  NttTables tabs;
+  const uint32_t* zinv = nullptr;
+  KG_TRY(ntt_tables(ctx, log_n, 0, &tabs, &zinv));
   const size_t n = (size_t)1 << log_n;
-  hipLaunchKernelGGL(k_scale_const, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_data, n, T->zinv);
+  hipLaunchKernelGGL(k_scale_const, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_data, n, zinv);
   KG_HIP(ctx, hipGetLastError());
   return KG_OK;
 }

@@ -3,10 +3,11 @@
 // A transform of up to 2^11 elements is ONE workgroup (ntt.hip: a single row step, ntiles == 1), so a host with B polynomials of one
 // size -- the idft -> coset_dft chains of groth16/src/prover.rs:36-41, the columns of a trace -- paid B launches that each used under
 // 1 % of the chip.  The tile code (ntt_tile.h) reads blockIdx.x only, so the grid's y dimension carries the transform's index here: the
-// kernel below is k_ntt_tile (ntt.hip) with `in` and `out` advanced by blockIdx.y times a per-step element stride (ntt_batch.h), and every
-// step of the plan is one launch for a whole group of transforms.  Twiddle tables are the context's cached ones (ntt_tables), shared by
-// all transforms of the batch.  The single-transform path of ntt.hip is not touched; this file is a translation unit of its own so that
-// its instantiations compile beside ntt.hip's instead of doubling that file's compile time.
+// kernel below runs k_ntt_tile's body (ntt_tile_run) with `in` and `out` advanced by blockIdx.y times a per-step element stride
+// (ntt_batch.h), and every step of the plan is one launch for a whole group of transforms.  Twiddle tables are the context's cached ones
+// (ntt_tables), shared by all transforms of the batch.  One body, two kernel shells: k_ntt_tile given the two strides and a grid of
+// (tiles, 1) takes 6 VGPRs more in four of its shapes, and two of them lose a wave per SIMD (EXPERIMENTS.md Part S).  This file is a
+// translation unit of its own so that its instantiations compile beside ntt.hip's instead of doubling that file's compile time.
 #include "common.h"
 #include "ntt_core.h"
 #include "ntt_tile.h"
@@ -18,32 +19,15 @@ static_assert(NTT_BATCH_ONE_STEP_MAX_LOG == (uint32_t)NTT_MAX_LOG_M, "ntt_batch.
 
 namespace {
 
-#ifndef KG_NTT_WAVES
-#define KG_NTT_WAVES 4      // as k_ntt_tile (ntt.hip)
-#endif
 // k_ntt_tile over a group of transforms: workgroup (x, y) runs tile x of transform y.  in_stride / out_stride: elements between two
 // transforms in the step's source and destination (one element = 4 words).
 template <int LOG_M, int LOG_TC, bool ROW>
 __global__ void __launch_bounds__((NttTile<Fr, LOG_M, LOG_TC, ROW>::NT)) __attribute__((amdgpu_waves_per_eu(KG_NTT_WAVES))) k_ntt_tile_batch(NttStepArgs A, size_t in_stride, size_t out_stride) {   // <= 128 VGPRs: LDS admits four waves per SIMD
   KG_SERVICE_PRIO();
-  using T = NttTile<Fr, LOG_M, LOG_TC, ROW>;
   extern __shared__ uint32_t lds[];
   A.in += (size_t)blockIdx.y * in_stride * 4;
   A.out += (size_t)blockIdx.y * out_stride * 4;
-  uint32_t tile = blockIdx.x;
-  if (A.tile_shift) tile = ((tile & 7u) << A.tile_shift) | (tile >> 3);     // workgroup i runs on XCD i mod 8: neighbouring tiles share an L2
-  const T t{A, tile};
-  const LdsPlanes<T::ELEMS> st{lds};
-  t.first(threadIdx.x, st);
-  if constexpr (!T::SINGLE) {
-    const auto full = [] { __syncthreads(); };
-    // between two wave-private passes: the wave's own LDS writes are ordered before its reads by the in-order LDS queue; the
-    // fence keeps the compiler from moving them across the boundary
-    const auto wave = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
-    t.after_first(full, wave);
-    t.template mids<T::G0>(threadIdx.x, st, full, wave);
-    t.last(threadIdx.x, st);
-  }
+  ntt_tile_run<NttTile<Fr, LOG_M, LOG_TC, ROW>>(A, lds);
 }
 
 // element i of transform b *= c   (c: one internal-form constant in device memory); workgroups of transform b: blockIdx.y = b
@@ -61,30 +45,18 @@ __global__ void __launch_bounds__(256) k_scale_const_batch(uint64_t* __restrict_
 
 // ---- dispatch: the shapes launch_step (ntt.hip) dispatches, batched ------------------------------------------------------------
 template <int LOG_M, int LOG_TC, bool ROW>
-int launch_tile_batch(kg_ctx* ctx, hipStream_t st, const NttStepArgs& a, uint32_t ntiles, uint32_t group, NttBatchStrides s) {
+int launch_tile_batch(NttShape<LOG_M, LOG_TC, ROW>, kg_ctx* ctx, hipStream_t st, const NttStepArgs& a, uint32_t ntiles, uint32_t group, NttBatchStrides s) {
   using T = NttTile<Fr, LOG_M, LOG_TC, ROW>;
-  const size_t lds_bytes = T::SINGLE ? 0 : (size_t)T::ELEMS * 36;
-  if (lds_bytes > 48 * 1024)               // more than the default dynamic LDS limit needs the attribute on THIS symbol (per device: set at every launch)
-    KG_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_tile_batch<LOG_M, LOG_TC, ROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  hipLaunchKernelGGL((k_ntt_tile_batch<LOG_M, LOG_TC, ROW>), dim3(ntiles, group), dim3(T::NT), lds_bytes, st, a, s.in, s.out);
+  if (T::LDS_BYTES > 48 * 1024)            // more than the default dynamic LDS limit needs the attribute on THIS symbol (per device: set at every launch)
+    KG_HIP(ctx, hipFuncSetAttribute((const void*)k_ntt_tile_batch<LOG_M, LOG_TC, ROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)T::LDS_BYTES));
+  hipLaunchKernelGGL((k_ntt_tile_batch<LOG_M, LOG_TC, ROW>), dim3(ntiles, group), dim3(T::NT), T::LDS_BYTES, st, a, s.in, s.out);
   return KG_OK;
 }
 int launch_step_batch(kg_ctx* ctx, hipStream_t st, const NttStepDesc& d, const NttStepArgs& a, uint32_t ntiles, uint32_t group, NttBatchStrides s) {
-  const int key = d.log_m * 16 + d.log_tc;
-  if (!d.row) {
-    switch (key) {
-#define X(m, tc) case (m) * 16 + (tc): return launch_tile_batch<m, tc, false>(ctx, st, a, ntiles, group, s);
-      KG_NTT_SHAPES(X) KG_NTT_SHAPES_COL_ONLY(X)
-#undef X
-    }
-  } else {
-    switch (key) {
-#define X(m, tc) case (m) * 16 + (tc): return launch_tile_batch<m, tc, true>(ctx, st, a, ntiles, group, s);
-      KG_NTT_SHAPES(X) KG_NTT_SHAPES_ROW_ONLY(X)
-#undef X
-    }
-  }
-  return set_err(ctx, KG_ERR_UNSUPPORTED, "ntt tile shape not instantiated");
+  int rc = KG_OK;
+  if (!ntt_for_shape(d, [&](auto shape) { rc = launch_tile_batch(shape, ctx, st, a, ntiles, group, s); }))
+    return set_err(ctx, KG_ERR_UNSUPPORTED, "ntt tile shape not instantiated");
+  return rc;
 }
 
 }  // namespace

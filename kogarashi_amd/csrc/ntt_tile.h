@@ -295,6 +295,7 @@ struct NttTile {
   static constexpr bool SINGLE = LOG_M <= 2;                // one pass: load -> butterflies -> store, no LDS
   static constexpr int S_LAST = LOG_M - 2;                  // first stage index of the last pass (fused with the store)
   static constexpr int M = 1 << LOG_M, TC = 1 << LOG_TC;
+  static constexpr size_t LDS_BYTES = SINGLE ? 0 : (size_t)ELEMS * 36;       // dynamic LDS of a launch: nine limb planes
   // wave-private passes (see above): tiles of at least four waves, lanes and blocks as thread bits 0..5 / 6..
 #ifdef KG_NTT_NO_WAVE_PRIVATE
   static constexpr bool WAVE_OK = false;
@@ -471,6 +472,35 @@ struct NttTile {
   }
 };
 
+#if defined(__HIPCC__)
+#ifndef KG_NTT_WAVES
+#define KG_NTT_WAVES 4       // amdgpu_waves_per_eu of both kernel shells: <= 128 VGPRs, LDS admits four waves per SIMD
+#endif
+// One tile by its workgroup, T = NttTile<Fr, ...>: the body of both kernel shells (k_ntt_tile, ntt.hip; k_ntt_tile_batch, ntt_batch.hip, which
+// advances A.in / A.out to its transform first).  Reads blockIdx.x only.
+template <class T>
+__device__ __forceinline__ void ntt_tile_run(const NttStepArgs& A, uint32_t* lds) {
+  uint32_t tile = blockIdx.x;
+  if (A.tile_shift) tile = ((tile & 7u) << A.tile_shift) | (tile >> 3);     // workgroup i runs on XCD i mod 8: neighbouring tiles share an L2
+  const T t{A, tile};
+  const LdsPlanes<T::ELEMS> st{lds};
+  t.first(threadIdx.x, st);
+  if constexpr (!T::SINGLE) {
+    // between two wave-private passes: the wave's own LDS writes are ordered before its reads by the in-order LDS queue; the
+    // fence keeps the compiler from moving them across the boundary
+    const auto wave = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); };
+#ifdef KG_NTT_EXP_NOBAR      // phase-off experiment (tools/dbg): no workgroup barriers (results are wrong, timing only)
+    const auto full = wave;
+#else
+    const auto full = [] { __syncthreads(); };
+#endif
+    t.after_first(full, wave);
+    t.template mids<T::G0>(threadIdx.x, st, full, wave);
+    t.last(threadIdx.x, st);
+  }
+}
+#endif
+
 }  // namespace kg
 
 // ---- table entries (shared by the device table kernels and the host test) ----------------------------------------
@@ -507,13 +537,21 @@ struct NttStepDesc { int log_m, log_tc; bool row; };
 #define KG_NTT_SHAPES(X) X(6, 4) X(7, 3) X(7, 4) X(8, 2) X(8, 3) X(9, 1) X(9, 2) X(10, 1) X(11, 1)
 #define KG_NTT_SHAPES_COL_ONLY(X) X(10, 0) X(11, 0)
 #define KG_NTT_SHAPES_ROW_ONLY(X) X(1, 0) X(2, 0) X(3, 0) X(4, 0) X(5, 0) X(6, 0) X(7, 0) X(8, 0) X(9, 0) X(10, 0) X(11, 0)
-inline bool ntt_shape_exists(int log_m, int log_tc, bool row) {
-#define X(m, tc) if (log_m == (m) && log_tc == (tc)) return true;
-  KG_NTT_SHAPES(X)
-  if (row) { KG_NTT_SHAPES_ROW_ONLY(X) } else { KG_NTT_SHAPES_COL_ONLY(X) }
+// the one place that expands the lists: fn(NttShape<...>{}) for the step's shape; false: that shape does not exist.  A switch per step
+// kind, column steps first, as the two launchers had it: the tile kernels are emitted in this order, and ntt.hip's code object is then
+// laid out as it was (with the row shapes first the looped one-workgroup transforms measured 1-2 % slower: measured, not understood,
+// EXPERIMENTS.md Part S)
+template <int LOG_M, int LOG_TC, bool ROW> struct NttShape {};
+template <class Fn>
+inline bool ntt_for_shape(const NttStepDesc& d, Fn&& fn) {
+#define X(m, tc) case (m) * 16 + (tc): fn(NttShape<m, tc, ROW>{}); return true;
+  const int key = d.log_m * 16 + d.log_tc;
+  if (!d.row) { constexpr bool ROW = false; switch (key) { KG_NTT_SHAPES(X) KG_NTT_SHAPES_COL_ONLY(X) } }
+  else { constexpr bool ROW = true; switch (key) { KG_NTT_SHAPES(X) KG_NTT_SHAPES_ROW_ONLY(X) } }
 #undef X
   return false;
 }
+inline bool ntt_shape_exists(int log_m, int log_tc, bool row) { return ntt_for_shape({log_m, log_tc, row}, [](auto) {}); }
 inline int ntt_tile_log(int log_m, int want, bool forced = false) {   // tile = 2^(log_m + log_tc) elements: 1024, 2048 or 4096
   const int least = forced ? log_m : log_m + 1;        // automatic plans keep at least two adjacent DFTs per tile (64-byte runs)
   return want < least ? least : want;

@@ -7,7 +7,7 @@
 //   k_points_check<Fq2, true>  the same, then the order-r test of the twist for the lanes that passed (points_check.h: ~95 point operations
 //                              on XYZZ<Fq2>, the register footprint of k_acc_tasks<Fq2>).
 // Both write the status byte and fold the summary in the same launch: per 64-lane workgroup one ballot, one 64-bit atomicAdd of the popcount
-// and one 64-bit atomicMin of the lowest bad index, into two words of the context that k_points_init sets to (0, n) on the stream first.
+// and one 64-bit atomicMin of the lowest bad index, into two words of the context that k_summary_init (common.h) sets to (0, n) on the stream first.
 #include "common.h"
 #include "points_check.h"
 
@@ -21,11 +21,6 @@ namespace {
 constexpr size_t WS_SUMMARY = 16;                               // bad count | first bad index
 constexpr size_t WS_HOST_XY = (3 * 8 + 2 * 16) * 8;             // the five host points of a CRS: alpha_g1 | beta_g1 | delta_g1 | beta_g2 | delta_g2
 constexpr size_t WS_BYTES = WS_SUMMARY + WS_HOST_XY + 16;       // + their flags
-
-__global__ void k_points_init(unsigned long long* summary, unsigned long long n) {
-  summary[0] = 0;
-  summary[1] = n;
-}
 
 // 64-lane workgroups: the subgroup chain keeps an XYZZ<Fq2> accumulator, the affine point and the temporaries of an addition live, and a
 // one-wave workgroup lets the compiler take what it needs of the register file (VGPRs + AGPRs) before it reaches for scratch memory
@@ -45,11 +40,10 @@ __global__ void __launch_bounds__(64) k_points_check(const uint64_t* __restrict_
     }
     if (status) status[i] = st;
   }
-  const unsigned long long bad = __ballot(st != 0);             // 64-lane workgroup = one wave
-  if (bad != 0 && threadIdx.x == 0) {
-    atomicAdd(&summary[0], (unsigned long long)__popcll(bad));
-    atomicMin(&summary[1], (unsigned long long)blockIdx.x * 64 + (unsigned long long)(__ffsll((long long)bad) - 1));
-  }
+  // 64-lane workgroup = one wave; thread 0 speaks for it (summary_fold's lowest bad lane changes the subgroup kernel's register split: 133 AGPRs for 134)
+  const unsigned long long bad = __ballot(st != 0);
+  if (bad != 0 && threadIdx.x == 0)
+    summary_add(summary, (unsigned long long)__popcll(bad), (unsigned long long)blockIdx.x * 64 + (unsigned long long)(__ffsll((long long)bad) - 1));
 }
 
 int ensure_ws_points(kg_ctx* c) {
@@ -74,19 +68,14 @@ int run_check(kg_ctx* c, int curve, const uint64_t* d_xy, const uint8_t* d_inf, 
   if (n >= ((size_t)1 << 37)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^37 points");       // the grid's x dimension
   KG_TRY(ensure_ws_points(c));
   unsigned long long* summary = (unsigned long long*)c->ws_points;
-  hipLaunchKernelGGL(k_points_init, dim3(1), dim3(1), 0, c->stream, summary, (unsigned long long)n);
+  hipLaunchKernelGGL(k_summary_init<unsigned long long>, dim3(1), dim3(1), 0, c->stream, summary, (unsigned long long)n, (uint32_t*)nullptr);
   const bool sub = (checks & KG_CHECK_SUBGROUP) != 0;
   if (curve == KG_G1) launch_check<Fq, false>(c, d_xy, d_inf, n, d_status, summary);
   else if (curve == KG_GRUMPKIN) launch_check<Fr, false>(c, d_xy, d_inf, n, d_status, summary);
   else if (sub) launch_check<Fq2, true>(c, d_xy, d_inf, n, d_status, summary);
   else launch_check<Fq2, false>(c, d_xy, d_inf, n, d_status, summary);
   KG_HIP(c, hipGetLastError());
-  unsigned long long h[2] = {0, 0};
-  KG_HIP(c, hipMemcpyAsync(h, summary, sizeof h, hipMemcpyDeviceToHost, c->stream));
-  KG_HIP(c, hipStreamSynchronize(c->stream));
-  if (out_bad) *out_bad = (size_t)h[0];
-  if (out_first_bad) *out_first_bad = (size_t)h[1];
-  return KG_OK;
+  return summary_read(c, summary, out_bad, out_first_bad);
 }
 
 bool checks_ok(int checks) { return checks != 0 && (checks & ~(KG_CHECK_CURVE | KG_CHECK_SUBGROUP)) == 0; }

@@ -125,49 +125,52 @@ __device__ __forceinline__ void row_dot(const uint64_t* __restrict__ row_ptr, co
   }
 }
 
-// Matrix-vector product in two launches.  Constraint rows hold a handful of terms, so a lane takes a whole row (a wave per
-// row kept 63 of 64 lanes idle: 0.45 ms per 2^18-row product); a row of more than SHORT_ROW terms -- the transposed systems
-// of the setup have one per heavily used wire, the constant-one wire touching every constraint -- is put on a work list
-// instead and summed by a whole wave in the second launch.
+// The sparse-row scheme, once for the matrix-vector product, Nova's cross term and the satisfiability check: two launches.  Constraint rows
+// hold a handful of terms (1.3 per matrix in the chain circuit), so a lane takes a whole row (k_rows_lane): a wave per row kept 63 of 64
+// lanes idle (0.45 ms per 2^18-row product), 8 lanes per row ran the cross term at 230 GB/s of algorithmic traffic (1.17 ms at 2^20 rows,
+// instruction-bound) and paid shuffle-tree merges for nothing.  A row of more than SHORT_ROW terms -- a range check's bit sum: 254; the
+// transposed systems of the setup have one per heavily used wire, the constant-one wire touching every constraint -- would hold its whole
+// wave for ~0.5 us per term and z vector: it is put on a work list instead and gets a whole wave in the second launch (k_rows_wave).
+// What a row is and does comes from the operation Op:
+//   int klass(row)                       0: the lane takes the row; 1: the list's front (a wave); 2: the list's back (a workgroup: the product's
+//                                        k_r1cs_rows_huge)
+//   template <int G> bool row(row, lane) the row by G lanes -- G = 1: lane = 0; G = 64: every lane of the wave, lane 0 finishes; true (lane 0
+//                                        only): the row is bad
+//   REPORTS                              bad rows are folded into ws.summary: the lowest bad lane speaks for its 64 rows, a wave of
+//                                        k_rows_wave for the rows it took (the list is in no particular order)
 constexpr uint32_t SHORT_ROW = 48;
 constexpr uint32_t HUGE_ROW = 4096;      // beyond: a 1024-lane workgroup per row (the constant-one wire's row of a transposed system: an entry per constraint)
-template <class P>
-__global__ void __launch_bounds__(256) k_r1cs_rows_short(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
-                                                         const uint64_t* __restrict__ val, size_t m, const uint64_t* __restrict__ z,
-                                                         uint64_t* __restrict__ out, uint32_t* __restrict__ long_rows, uint32_t* __restrict__ long_count) {
+struct CsrView {
+  const uint64_t* row_ptr; const uint64_t* col; const uint64_t* val;
+  __device__ __forceinline__ uint64_t len(size_t row) const { return row_ptr[row + 1] - row_ptr[row]; }
+};
+template <class Op>
+__global__ void __launch_bounds__(256) k_rows_lane(Op op, size_t m, RowWs ws) {
   KG_SERVICE_PRIO();
   const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= m) return;
-  const uint64_t len = row_ptr[row + 1] - row_ptr[row];
-  if (len > SHORT_ROW) {      // work lists: long rows from the front of the list (a wave each), huge rows from its back (a workgroup each)
-    if (len > HUGE_ROW) long_rows[m - 1 - atomicAdd(long_count + 1, 1u)] = (uint32_t)row;
-    else long_rows[atomicAdd(long_count, 1u)] = (uint32_t)row;
-    return;
+  bool bad = false;                                       // lanes past the end and lanes whose row went to a work list report nothing
+  if (row < m) {
+    const int k = op.klass(row);
+    if (k == 2) ws.list[m - 1 - atomicAdd(ws.count + 1, 1u)] = (uint32_t)row;
+    else if (k == 1) ws.list[atomicAdd(ws.count, 1u)] = (uint32_t)row;
+    else bad = op.template row<1>(row, 0);
   }
-  Fp<P> sum[1];
-  row_dot<P, 1, 1>(row_ptr, col, val, row, 0, z, z, sum);
-  uint32_t wo[8];
-  words_from_limbs(reduce_2p(mul(sum[0], Fp<P>::from_const(P::C_FROM_REF))), wo);        // raw product domain -> the ABI's
-  store_words(out, row, wo);
+  if constexpr (Op::REPORTS) summary_fold(ws.summary, bad, (uint32_t)row);
 }
-template <class P>
-__global__ void __launch_bounds__(256) k_r1cs_rows_long(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
-                                                        const uint64_t* __restrict__ val, const uint64_t* __restrict__ z, uint64_t* __restrict__ out,
-                                                        const uint32_t* __restrict__ long_rows, const uint32_t* __restrict__ long_count) {
+// (the list as const __restrict__ parameters: handed over as a RowWs, the cross term's and the check's instances take one VGPR more)
+template <class Op>
+__global__ void __launch_bounds__(256) k_rows_wave(Op op, uint32_t* __restrict__ summary, const uint32_t* __restrict__ list, const uint32_t* __restrict__ count) {
   KG_SERVICE_PRIO();
   const uint32_t nwaves = gridDim.x * (blockDim.x >> 6), wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
-  const uint32_t total = *long_count;
+  const uint32_t total = *count;
+  uint32_t n_bad = 0, first = 0xffffffffu;                // lane 0 keeps them
   for (uint32_t i = wave; i < total; i += nwaves) {      // wave-uniform trip count: the shuffles inside row_dot see full waves
-    const size_t row = long_rows[i];
-    Fp<P> sum[1];
-    row_dot<P, 64, 1>(row_ptr, col, val, row, lane, z, z, sum);
-    if (lane == 0) {
-      uint32_t wo[8];
-      words_from_limbs(reduce_2p(mul(sum[0], Fp<P>::from_const(P::C_FROM_REF))), wo);
-      store_words(out, row, wo);
-    }
+    const size_t row = list[i];
+    if (op.template row<64>(row, lane)) { ++n_bad; first = min(first, (uint32_t)row); }
   }
+  if constexpr (Op::REPORTS)
+    if (lane == 0 && n_bad != 0) summary_add(summary, n_bad, first);
 }
 
 // A HUGE row (more than HUGE_ROW entries) per WORKGROUP: 1024 lanes stride over its entries; wave sums by shuffles, the sixteen wave sums
@@ -215,52 +218,49 @@ __global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge(const uint64_t* __re
   }
 }
 
-// Nova's cross term (nova/src/prover.rs:53-90): T = AZ1 o BZ2 + AZ2 o BZ1 - u1 * CZ2 - u2 * CZ1, one kernel: every matrix row
-// is read once for both z vectors, the six matrix-vector products never touch memory.  ONE lane per constraint row: R1CS
-// rows hold a handful of terms (1.3 per matrix in the chain circuit), so a lane group per row leaves most lanes idle in the
-// entry loops and pays shuffle-tree merges for nothing -- 8 lanes per row ran at 230 GB/s of algorithmic traffic
-// (1.17 ms at 2^20 rows, instruction-bound), this form is bound by its ~12 products per row.  A long row only delays its own wave.
-// u1s, u2s: u * 2^266 as limbs (host-side), the factor form cross_term_row wants next to raw row sums.
-struct CsrView { const uint64_t* row_ptr; const uint64_t* col; const uint64_t* val; };
-struct Limbs9 { uint32_t l[9]; };
+// out = M z  (zkstd/src/matrix/row.rs:43-51, matrix.rs:36-48): long rows to the list's front, huge rows to its back
 template <class P>
-__global__ void __launch_bounds__(256) k_nova_cross_term(CsrView A, CsrView B, CsrView C, size_t m, const uint64_t* __restrict__ z1,
-                                                         const uint64_t* __restrict__ z2, Limbs9 u1s, Limbs9 u2s, uint64_t* __restrict__ out,
-                                                         uint32_t* __restrict__ long_rows, uint32_t* __restrict__ long_count) {
-  KG_SERVICE_PRIO();
-  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= m) return;
-  // a constraint with a long linear combination (a range check's bit sum: 254 terms) would hold its whole wave for ~0.5 us per term and
-  // z vector: such rows go to a work list and get a wave each (k_nova_cross_term_long)
-  if (A.row_ptr[row + 1] - A.row_ptr[row] > SHORT_ROW || B.row_ptr[row + 1] - B.row_ptr[row] > SHORT_ROW || C.row_ptr[row + 1] - C.row_ptr[row] > SHORT_ROW) {
-    long_rows[atomicAdd(long_count, 1u)] = (uint32_t)row;
-    return;
+struct ProdOp {
+  static constexpr bool REPORTS = false;
+  CsrView M; const uint64_t* z; uint64_t* out;
+  __device__ __forceinline__ int klass(size_t row) const { const uint64_t len = M.len(row); return len > HUGE_ROW ? 2 : (len > SHORT_ROW ? 1 : 0); }
+  template <int G>
+  __device__ __forceinline__ bool row(size_t row, int lane) const {
+    Fp<P> sum[1];
+    row_dot<P, G, 1>(M.row_ptr, M.col, M.val, row, lane, z, z, sum);
+    if (lane == 0) {
+      uint32_t wo[8];
+      words_from_limbs(reduce_2p(mul(sum[0], Fp<P>::from_const(P::C_FROM_REF))), wo);        // raw product domain -> the ABI's
+      store_words(out, row, wo);
+    }
+    return false;
   }
-  Fp<P> az[2], bz[2], cz[2];
-  row_dot<P, 1, 2>(A.row_ptr, A.col, A.val, row, 0, z1, z2, az);
-  row_dot<P, 1, 2>(B.row_ptr, B.col, B.val, row, 0, z1, z2, bz);
-  row_dot<P, 1, 2>(C.row_ptr, C.col, C.val, row, 0, z1, z2, cz);
-  const Fp<P> r = cross_term_row(az[0], az[1], bz[0], bz[1], cz[0], cz[1], Fp<P>::from_const(u1s.l), Fp<P>::from_const(u2s.l),
-                                 Fp<P>::from_const(P::C_XT_HAD));
-  uint32_t wo[8];
-  words_from_limbs(reduce_2p(r), wo);
-  store_words(out, row, wo);
-}
+};
 
+// The two operations over a whole R1CS: a row is long when it has more than SHORT_ROW entries in ANY of the three matrices; every matrix row
+// is read once, for one or two z vectors, and the row sums never touch memory
+struct Csr3 {
+  CsrView A, B, C;
+  __device__ __forceinline__ int klass(size_t row) const { return A.len(row) > SHORT_ROW || B.len(row) > SHORT_ROW || C.len(row) > SHORT_ROW; }
+  template <class P, int G, int NZ>
+  __device__ __forceinline__ void dots(size_t row, int lane, const uint64_t* z1, const uint64_t* z2, Fp<P> (&az)[NZ], Fp<P> (&bz)[NZ], Fp<P> (&cz)[NZ]) const {
+    row_dot<P, G, NZ>(A.row_ptr, A.col, A.val, row, lane, z1, z2, az);
+    row_dot<P, G, NZ>(B.row_ptr, B.col, B.val, row, lane, z1, z2, bz);
+    row_dot<P, G, NZ>(C.row_ptr, C.col, C.val, row, lane, z1, z2, cz);
+  }
+};
+struct Limbs9 { uint32_t l[9]; };
+
+// Nova's cross term (nova/src/prover.rs:53-90): T = AZ1 o BZ2 + AZ2 o BZ1 - u1 * CZ2 - u2 * CZ1; bound by its ~12 products per row.
+// u1s, u2s: u * 2^266 as limbs (host-side), the factor form cross_term_row wants next to raw row sums.
 template <class P>
-__global__ void __launch_bounds__(256) k_nova_cross_term_long(CsrView A, CsrView B, CsrView C, const uint64_t* __restrict__ z1, const uint64_t* __restrict__ z2,
-                                                              Limbs9 u1s, Limbs9 u2s, uint64_t* __restrict__ out, const uint32_t* __restrict__ long_rows,
-                                                              const uint32_t* __restrict__ long_count) {
-  KG_SERVICE_PRIO();
-  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6), wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  const uint32_t total = *long_count;
-  for (uint32_t i = wave; i < total; i += nwaves) {      // wave-uniform trip count: the shuffles inside row_dot see full waves
-    const size_t row = long_rows[i];
+struct CrossOp : Csr3 {
+  static constexpr bool REPORTS = false;
+  const uint64_t *z1, *z2; Limbs9 u1s, u2s; uint64_t* out;
+  template <int G>
+  __device__ __forceinline__ bool row(size_t row, int lane) const {
     Fp<P> az[2], bz[2], cz[2];
-    row_dot<P, 64, 2>(A.row_ptr, A.col, A.val, row, lane, z1, z2, az);
-    row_dot<P, 64, 2>(B.row_ptr, B.col, B.val, row, lane, z1, z2, bz);
-    row_dot<P, 64, 2>(C.row_ptr, C.col, C.val, row, lane, z1, z2, cz);
+    dots<P, G, 2>(row, lane, z1, z2, az, bz, cz);
     if (lane == 0) {
       const Fp<P> r = cross_term_row(az[0], az[1], bz[0], bz[1], cz[0], cz[1], Fp<P>::from_const(u1s.l), Fp<P>::from_const(u2s.l),
                                      Fp<P>::from_const(P::C_XT_HAD));
@@ -268,82 +268,34 @@ __global__ void __launch_bounds__(256) k_nova_cross_term_long(CsrView A, CsrView
       words_from_limbs(reduce_2p(r), wo);
       store_words(out, row, wo);
     }
+    return false;
   }
-}
+};
 
 // kg_r1cs_check: is (A z)_i (B z)_i = u (C z)_i + E_i for every row?  (nova/src/relaxed_r1cs.rs:81-114 is_sat_relaxed; u = 1 and E = 0:
-// zkstd/src/r1cs.rs:62-77 is_sat.)  The shape of the cross term with one z vector: a lane per row, the three row sums stay in registers,
-// rows with more than SHORT_ROW entries in any matrix go to the work list and get a wave each in the second launch.  Instead of an
-// element per row the kernels leave a status byte (when asked) and two summary words: per wave one ballot, and -- only for a wave that
-// holds a bad row -- one atomicAdd of the popcount and one atomicMin of the lowest bad row.  summary[0] = count, summary[1] = first index,
-// set to (0, m) on the stream by k_r1cs_check_init before every call (row indices are below 2^32).
+// zkstd/src/r1cs.rs:62-77 is_sat.)  The shape of the cross term with one z vector; instead of an element per row it leaves a status byte
+// (when asked) and the summary (common.h; row indices are below 2^32).
 // us: u * 2^266 as limbs (host-side, like the cross term's).  e == nullptr: E = 0, nothing is read.
-__global__ void k_r1cs_check_init(uint32_t* long_count, uint32_t* summary, uint32_t m) {
-  long_count[0] = 0;
-  summary[0] = 0;
-  summary[1] = m;
-}
 template <class P>
-__device__ __forceinline__ bool row_unsat(const Fp<P>& az, const Fp<P>& bz, const Fp<P>& cz, const Limbs9& us, const uint64_t* __restrict__ e, size_t row) {
-  Fp<P> er = Fp<P>::zero();
-  if (e != nullptr) {
-    uint32_t we[8];
-    load_words(e, row, we);
-    er = limbs_from_words<P>(we);
-  }
-  return !is_zero_mod_p(sat_residual_row(az, bz, cz, Fp<P>::from_const(us.l), er, Fp<P>::from_const(P::C_XT_HAD)));
-}
-template <class P>
-__global__ void __launch_bounds__(256) k_r1cs_check(CsrView A, CsrView B, CsrView C, size_t m, const uint64_t* __restrict__ z, Limbs9 us,
-                                                    const uint64_t* __restrict__ e, uint8_t* __restrict__ status, uint32_t* __restrict__ summary,
-                                                    uint32_t* __restrict__ long_rows, uint32_t* __restrict__ long_count) {
-  KG_SERVICE_PRIO();
-  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;                                       // lanes past the end and lanes whose row went to the work list report nothing
-  if (row < m) {
-    if (A.row_ptr[row + 1] - A.row_ptr[row] > SHORT_ROW || B.row_ptr[row + 1] - B.row_ptr[row] > SHORT_ROW || C.row_ptr[row + 1] - C.row_ptr[row] > SHORT_ROW) {
-      long_rows[atomicAdd(long_count, 1u)] = (uint32_t)row;
-    } else {
-      Fp<P> az[1], bz[1], cz[1];
-      row_dot<P, 1, 1>(A.row_ptr, A.col, A.val, row, 0, z, z, az);
-      row_dot<P, 1, 1>(B.row_ptr, B.col, B.val, row, 0, z, z, bz);
-      row_dot<P, 1, 1>(C.row_ptr, C.col, C.val, row, 0, z, z, cz);
-      bad = row_unsat<P>(az[0], bz[0], cz[0], us, e, row);
-      if (status != nullptr) status[row] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
-    }
-  }
-  const unsigned long long mask = __ballot(bad);          // this wave's 64 rows
-  if (mask != 0 && (threadIdx.x & 63) == __ffsll((long long)mask) - 1) {       // the lowest bad lane speaks for its wave: its row is the wave's first
-    atomicAdd(&summary[0], (uint32_t)__popcll(mask));
-    atomicMin(&summary[1], (uint32_t)row);
-  }
-}
-template <class P>
-__global__ void __launch_bounds__(256) k_r1cs_check_long(CsrView A, CsrView B, CsrView C, const uint64_t* __restrict__ z, Limbs9 us,
-                                                         const uint64_t* __restrict__ e, uint8_t* __restrict__ status, uint32_t* __restrict__ summary,
-                                                         const uint32_t* __restrict__ long_rows, const uint32_t* __restrict__ long_count) {
-  KG_SERVICE_PRIO();
-  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6), wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  const uint32_t total = *long_count;
-  uint32_t n_bad = 0, first = 0xffffffffu;                // of this wave's rows (the list is in no particular order); lane 0 keeps them
-  for (uint32_t i = wave; i < total; i += nwaves) {      // wave-uniform trip count: the shuffles inside row_dot see full waves
-    const size_t row = long_rows[i];
+struct CheckOp : Csr3 {
+  static constexpr bool REPORTS = true;
+  const uint64_t* z; Limbs9 us; const uint64_t* e; uint8_t* status;
+  template <int G>
+  __device__ __forceinline__ bool row(size_t row, int lane) const {
     Fp<P> az[1], bz[1], cz[1];
-    row_dot<P, 64, 1>(A.row_ptr, A.col, A.val, row, lane, z, z, az);
-    row_dot<P, 64, 1>(B.row_ptr, B.col, B.val, row, lane, z, z, bz);
-    row_dot<P, 64, 1>(C.row_ptr, C.col, C.val, row, lane, z, z, cz);
-    if (lane == 0) {
-      const bool bad = row_unsat<P>(az[0], bz[0], cz[0], us, e, row);
-      if (status != nullptr) status[row] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
-      if (bad) { ++n_bad; first = min(first, (uint32_t)row); }
+    dots<P, G, 1>(row, lane, z, z, az, bz, cz);
+    if (lane != 0) return false;
+    Fp<P> er = Fp<P>::zero();
+    if (e != nullptr) {
+      uint32_t we[8];
+      load_words(e, row, we);
+      er = limbs_from_words<P>(we);
     }
+    const bool bad = !is_zero_mod_p(sat_residual_row(az[0], bz[0], cz[0], Fp<P>::from_const(us.l), er, Fp<P>::from_const(P::C_XT_HAD)));
+    if (status != nullptr) status[row] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
+    return bad;
   }
-  if (lane == 0 && n_bad != 0) {
-    atomicAdd(&summary[0], n_bad);
-    atomicMin(&summary[1], first);
-  }
-}
+};
 
 // ---- splitmix64 streams (oracle/pyoracle.py stream_at, oracle/kg_oracle.c stream_words) ---------------
 __device__ __forceinline__ uint64_t splitmix_next(uint64_t& s) {
@@ -445,64 +397,82 @@ __global__ void __launch_bounds__(64) k_gen_bases(uint64_t seed, size_t start, s
   store_words(out, 2 * i + 1, wy);
 }
 
+// ---- host half --------------------------------------------------------------------------------------
+bool field_ok(int field) { return field == KG_FR || field == KG_FQ; }
+// fn(P{}) with the field's parameter type: every launch of a kernel templated on it goes through here
+template <class Fn>
+void by_field(int field, Fn&& fn) {
+  if (field == KG_FR) fn(FrParams{});
+  else fn(FqParams{});
+}
+dim3 grid256(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+template <class Op>
+void launch_rows(hipStream_t st, const Op& op, size_t m, const RowWs& ws) {
+  hipLaunchKernelGGL(k_rows_lane<Op>, grid256(m), dim3(256), 0, st, op, m, ws);
+  hipLaunchKernelGGL(k_rows_wave<Op>, dim3(256), dim3(256), 0, st, op, ws.summary, ws.list, ws.count);
+}
+CsrView view(const kg_csr* x) { return {x->d_row_ptr, x->d_col, x->d_val}; }
+// a, b, c all there, with all their arrays?
+bool csr3_ok(const kg_csr* a, const kg_csr* b, const kg_csr* cm) {
+  for (const kg_csr* x : {a, b, cm})
+    if (!x->d_row_ptr || !x->d_col || !x->d_val) return false;
+  return true;
+}
+
+// u * 2^266 mod p as limbs: ten modular doublings of the ABI form u * 2^256
+Limbs9 scaled(const uint64_t* h_u, bool fr) {
+  Limbs9 out;
+  uint64_t w64[4];
+  if (fr) { HostFr x = HostFr::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
+  else { HostFq x = HostFq::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
+  const Fp<FrParams> lim = limbs_from_words<FrParams>(words8(w64).w);        // the spreading is the same for both fields
+  for (int k = 0; k < 9; ++k) out.l[k] = lim.l[k];
+  return out;
+}
+
 }  // namespace
 
 extern "C" {
 
 int kg_field_vec_op(kg_ctx* c, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
-  if (!c || op < 0 || op > KG_OP_TO_MONT || (field != KG_FR && field != KG_FQ)) return KG_ERR_BAD_ARG;
+  if (!c || op < 0 || op > KG_OP_TO_MONT || !field_ok(field)) return KG_ERR_BAD_ARG;
   if (n == 0) return KG_OK;
   KG_HIP(c, hipSetDevice(c->device));
   const bool binary = (op == KG_OP_ADD || op == KG_OP_SUB || op == KG_OP_MUL);
   if (!a || !out || (binary && !b)) return KG_ERR_BAD_ARG;
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (field == KG_FR) hipLaunchKernelGGL(k_vec_op<FrParams>, grid, dim3(256), 0, c->stream, op, a, b, out, n);
-  else hipLaunchKernelGGL(k_vec_op<FqParams>, grid, dim3(256), 0, c->stream, op, a, b, out, n);
+  by_field(field, [&](auto p) { hipLaunchKernelGGL(k_vec_op<decltype(p)>, grid256(n), dim3(256), 0, c->stream, op, a, b, out, n); });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }
 
 int kg_field_vec_scale(kg_ctx* c, int field, const uint64_t* a, const uint64_t* h_s, uint64_t* out, size_t n) {
-  if (!c || !h_s || (field != KG_FR && field != KG_FQ)) return KG_ERR_BAD_ARG;
+  if (!c || !h_s || !field_ok(field)) return KG_ERR_BAD_ARG;
   if (n == 0) return KG_OK;
   KG_HIP(c, hipSetDevice(c->device));
   if (!a || !out) return KG_ERR_BAD_ARG;
-  Words8 s;
-  for (int i = 0; i < 4; ++i) { s.w[2 * i] = (uint32_t)h_s[i]; s.w[2 * i + 1] = (uint32_t)(h_s[i] >> 32); }
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (field == KG_FR) hipLaunchKernelGGL(k_vec_scale<FrParams>, grid, dim3(256), 0, c->stream, a, s, out, n);
-  else hipLaunchKernelGGL(k_vec_scale<FqParams>, grid, dim3(256), 0, c->stream, a, s, out, n);
+  by_field(field, [&](auto p) { hipLaunchKernelGGL(k_vec_scale<decltype(p)>, grid256(n), dim3(256), 0, c->stream, a, words8(h_s), out, n); });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }
 
 int kg_field_powers(kg_ctx* c, int field, const uint64_t* h_start, const uint64_t* h_base, uint64_t* out, size_t n) {
-  if (!c || !h_start || !h_base || (field != KG_FR && field != KG_FQ)) return KG_ERR_BAD_ARG;
+  if (!c || !h_start || !h_base || !field_ok(field)) return KG_ERR_BAD_ARG;
   if (n == 0) return KG_OK;
   KG_HIP(c, hipSetDevice(c->device));
   if (!out) return KG_ERR_BAD_ARG;
-  Words8 s, b;
-  for (int i = 0; i < 4; ++i) {
-    s.w[2 * i] = (uint32_t)h_start[i]; s.w[2 * i + 1] = (uint32_t)(h_start[i] >> 32);
-    b.w[2 * i] = (uint32_t)h_base[i]; b.w[2 * i + 1] = (uint32_t)(h_base[i] >> 32);
-  }
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (field == KG_FR) hipLaunchKernelGGL(k_powers<FrParams>, grid, dim3(256), 0, c->stream, s, b, out, n);
-  else hipLaunchKernelGGL(k_powers<FqParams>, grid, dim3(256), 0, c->stream, s, b, out, n);
+  const Words8 s = words8(h_start), b = words8(h_base);
+  by_field(field, [&](auto p) { hipLaunchKernelGGL(k_powers<decltype(p)>, grid256(n), dim3(256), 0, c->stream, s, b, out, n); });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }
 
 int kg_field_vec_axpy(kg_ctx* c, int field, const uint64_t* a, const uint64_t* h_s, const uint64_t* b, uint64_t* out, size_t n) {
-  if (!c || !h_s || (field != KG_FR && field != KG_FQ)) return KG_ERR_BAD_ARG;
+  if (!c || !h_s || !field_ok(field)) return KG_ERR_BAD_ARG;
   if (n == 0) return KG_OK;
   KG_HIP(c, hipSetDevice(c->device));
   if (!a || !b || !out) return KG_ERR_BAD_ARG;
-  Words8 s;
-  for (int i = 0; i < 4; ++i) { s.w[2 * i] = (uint32_t)h_s[i]; s.w[2 * i + 1] = (uint32_t)(h_s[i] >> 32); }
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (field == KG_FR) hipLaunchKernelGGL(k_vec_axpy<FrParams>, grid, dim3(256), 0, c->stream, a, s, b, out, n);
-  else hipLaunchKernelGGL(k_vec_axpy<FqParams>, grid, dim3(256), 0, c->stream, a, s, b, out, n);
+  by_field(field, [&](auto p) { hipLaunchKernelGGL(k_vec_axpy<decltype(p)>, grid256(n), dim3(256), 0, c->stream, a, words8(h_s), b, out, n); });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }
@@ -510,52 +480,29 @@ int kg_field_vec_axpy(kg_ctx* c, int field, const uint64_t* a, const uint64_t* h
 }  // extern "C"
 
 namespace kg {
-// The product on a queue of the caller's choice; scratch: (m + 16) words for the work list of long rows.
 int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
-                      const uint64_t* z, uint64_t* out, uint32_t* scratch) {
-  uint32_t* count = scratch;
-  uint32_t* list = scratch + 16;
-  KG_HIP(c, hipMemsetAsync(count, 0, 8, st));
-  const dim3 grid((unsigned)((m + 255) / 256));
-  if (field == KG_FR) {
-    hipLaunchKernelGGL(k_r1cs_rows_short<FrParams>, grid, dim3(256), 0, st, row_ptr, col, val, m, z, out, list, count);
-    hipLaunchKernelGGL(k_r1cs_rows_long<FrParams>, dim3(256), dim3(256), 0, st, row_ptr, col, val, z, out, list, count);
-    hipLaunchKernelGGL(k_r1cs_rows_huge<FrParams>, dim3(64), dim3(LONG_NT), 0, st, row_ptr, col, val, z, out, list, count, m);
-  } else {
-    hipLaunchKernelGGL(k_r1cs_rows_short<FqParams>, grid, dim3(256), 0, st, row_ptr, col, val, m, z, out, list, count);
-    hipLaunchKernelGGL(k_r1cs_rows_long<FqParams>, dim3(256), dim3(256), 0, st, row_ptr, col, val, z, out, list, count);
-    hipLaunchKernelGGL(k_r1cs_rows_huge<FqParams>, dim3(64), dim3(LONG_NT), 0, st, row_ptr, col, val, z, out, list, count, m);
-  }
+                      const uint64_t* z, uint64_t* out, const RowWs& ws) {
+  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, st));
+  by_field(field, [&](auto p) {
+    using P = decltype(p);
+    launch_rows(st, ProdOp<P>{{row_ptr, col, val}, z, out}, m, ws);
+    hipLaunchKernelGGL(k_r1cs_rows_huge<P>, dim3(64), dim3(LONG_NT), 0, st, row_ptr, col, val, z, out, ws.list, ws.count, m);
+  });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }
 }  // namespace kg
 
-namespace {
-// u * 2^266 mod p as limbs: ten modular doublings of the ABI form u * 2^256
-Limbs9 scaled(const uint64_t* h_u, bool fr) {
-  Limbs9 out;
-  uint64_t w64[4];
-  if (fr) { HostFr x = HostFr::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
-  else { HostFq x = HostFq::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
-  uint32_t w[8];
-  for (int i = 0; i < 4; ++i) { w[2 * i] = (uint32_t)w64[i]; w[2 * i + 1] = (uint32_t)(w64[i] >> 32); }
-  const Fp<FrParams> lim = limbs_from_words<FrParams>(w);        // the spreading is the same for both fields
-  for (int k = 0; k < 9; ++k) out.l[k] = lim.l[k];
-  return out;
-}
-}  // namespace
-
 extern "C" {
 
 int kg_r1cs_prod(kg_ctx* c, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z, uint64_t* out) {
-  if (!c || (field != KG_FR && field != KG_FQ)) return KG_ERR_BAD_ARG;
+  if (!c || !field_ok(field)) return KG_ERR_BAD_ARG;
   if (m == 0) return KG_OK;
   if (!row_ptr || !col || !val || !z || !out) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
-  KG_TRY(ensure_ws_vec(c, 3 * (m + 16) * 4));             // work lists of long rows (three: the prover runs three products at once)
-  return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, out, (uint32_t*)c->ws_vec);
+  KG_TRY(ensure_ws_vec(c, RowWs::bytes(m)));
+  return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, out, RowWs(c->ws_vec, m));
 }
 
 int kg_r1cs_evaluate(kg_ctx* c, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z, uint64_t* out) {
@@ -564,77 +511,47 @@ int kg_r1cs_evaluate(kg_ctx* c, const uint64_t* row_ptr, const uint64_t* col, co
 
 int kg_nova_cross_term(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z1,
                        const uint64_t* d_z2, const uint64_t* h_u1, const uint64_t* h_u2, uint64_t* d_out) {
-  if (!c || (field != KG_FR && field != KG_FQ) || !a || !b || !cm || !h_u1 || !h_u2) return KG_ERR_BAD_ARG;
+  if (!c || !field_ok(field) || !a || !b || !cm || !h_u1 || !h_u2) return KG_ERR_BAD_ARG;
   if (m == 0) return KG_OK;
-  if (!d_z1 || !d_z2 || !d_out) return KG_ERR_BAD_ARG;
-  for (const kg_csr* x : {a, b, cm})
-    if (!x->d_row_ptr || !x->d_col || !x->d_val) return KG_ERR_BAD_ARG;
+  if (!d_z1 || !d_z2 || !d_out || !csr3_ok(a, b, cm)) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
   const Limbs9 u1 = scaled(h_u1, field == KG_FR), u2 = scaled(h_u2, field == KG_FR);
-  const CsrView A{a->d_row_ptr, a->d_col, a->d_val}, B{b->d_row_ptr, b->d_col, b->d_val}, C{cm->d_row_ptr, cm->d_col, cm->d_val};
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
-  KG_TRY(ensure_ws_vec(c, 3 * (m + 16) * 4));             // the work list of long rows (same space as kg_r1cs_prod's)
-  uint32_t* count = (uint32_t*)c->ws_vec;
-  uint32_t* list = count + 16;
-  KG_HIP(c, hipMemsetAsync(count, 0, 8, c->stream));
-  const dim3 grid((unsigned)((m + 255) / 256));
-  if (field == KG_FR) {
-    hipLaunchKernelGGL(k_nova_cross_term<FrParams>, grid, dim3(256), 0, c->stream, A, B, C, m, d_z1, d_z2, u1, u2, d_out, list, count);
-    hipLaunchKernelGGL(k_nova_cross_term_long<FrParams>, dim3(256), dim3(256), 0, c->stream, A, B, C, d_z1, d_z2, u1, u2, d_out, list, count);
-  } else {
-    hipLaunchKernelGGL(k_nova_cross_term<FqParams>, grid, dim3(256), 0, c->stream, A, B, C, m, d_z1, d_z2, u1, u2, d_out, list, count);
-    hipLaunchKernelGGL(k_nova_cross_term_long<FqParams>, dim3(256), dim3(256), 0, c->stream, A, B, C, d_z1, d_z2, u1, u2, d_out, list, count);
-  }
+  KG_TRY(ensure_ws_vec(c, RowWs::bytes(m)));
+  const RowWs ws(c->ws_vec, m);
+  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, c->stream));
+  by_field(field, [&](auto p) { launch_rows(c->stream, CrossOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z1, d_z2, u1, u2, d_out}, m, ws); });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }
 
 int kg_r1cs_check(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z, const uint64_t* h_u,
                   const uint64_t* d_e, uint8_t* d_status, size_t* out_bad, size_t* out_first_bad) {
-  if (!c || (field != KG_FR && field != KG_FQ) || !a || !b || !cm) return KG_ERR_BAD_ARG;
+  if (!c || !field_ok(field) || !a || !b || !cm) return KG_ERR_BAD_ARG;
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
   if (m == 0) {
     if (out_bad) *out_bad = 0;
     if (out_first_bad) *out_first_bad = 0;
     return KG_OK;
   }
-  if (!d_z) return KG_ERR_BAD_ARG;
-  for (const kg_csr* x : {a, b, cm})
-    if (!x->d_row_ptr || !x->d_col || !x->d_val) return KG_ERR_BAD_ARG;
+  if (!d_z || !csr3_ok(a, b, cm)) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
   const bool fr = field == KG_FR;
   const Limbs9 us = scaled(h_u ? h_u : (fr ? HostFrP::ONE : HostFqP::ONE), fr);       // no u: the plain relation, u = 1
-  const CsrView A{a->d_row_ptr, a->d_col, a->d_val}, B{b->d_row_ptr, b->d_col, b->d_val}, C{cm->d_row_ptr, cm->d_col, cm->d_val};
-  KG_TRY(ensure_ws_vec(c, 3 * (m + 16) * 4));             // the work list of long rows (same space as kg_r1cs_prod's); words 2 and 3: the summary
-  uint32_t* count = (uint32_t*)c->ws_vec;
-  uint32_t* summary = count + 2;
-  uint32_t* list = count + 16;
-  hipLaunchKernelGGL(k_r1cs_check_init, dim3(1), dim3(1), 0, c->stream, count, summary, (uint32_t)m);
-  const dim3 grid((unsigned)((m + 255) / 256));
-  if (fr) {
-    hipLaunchKernelGGL(k_r1cs_check<FrParams>, grid, dim3(256), 0, c->stream, A, B, C, m, d_z, us, d_e, d_status, summary, list, count);
-    hipLaunchKernelGGL(k_r1cs_check_long<FrParams>, dim3(256), dim3(256), 0, c->stream, A, B, C, d_z, us, d_e, d_status, summary, list, count);
-  } else {
-    hipLaunchKernelGGL(k_r1cs_check<FqParams>, grid, dim3(256), 0, c->stream, A, B, C, m, d_z, us, d_e, d_status, summary, list, count);
-    hipLaunchKernelGGL(k_r1cs_check_long<FqParams>, dim3(256), dim3(256), 0, c->stream, A, B, C, d_z, us, d_e, d_status, summary, list, count);
-  }
+  KG_TRY(ensure_ws_vec(c, RowWs::bytes(m)));
+  const RowWs ws(c->ws_vec, m);
+  hipLaunchKernelGGL(k_summary_init<uint32_t>, dim3(1), dim3(1), 0, c->stream, ws.summary, (uint32_t)m, ws.count);
+  by_field(field, [&](auto p) { launch_rows(c->stream, CheckOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z, us, d_e, d_status}, m, ws); });
   KG_HIP(c, hipGetLastError());
-  uint32_t h[2] = {0, 0};
-  KG_HIP(c, hipMemcpyAsync(h, summary, sizeof h, hipMemcpyDeviceToHost, c->stream));
-  KG_HIP(c, hipStreamSynchronize(c->stream));
-  if (out_bad) *out_bad = (size_t)h[0];
-  if (out_first_bad) *out_first_bad = (size_t)h[1];
-  return KG_OK;
+  return summary_read(c, ws.summary, out_bad, out_first_bad);
 }
 
 int kg_gen_scalars(kg_ctx* c, int field, uint64_t seed, size_t start, size_t n, uint64_t* out) {
-  if (!c || (field != KG_FR && field != KG_FQ)) return KG_ERR_BAD_ARG;
+  if (!c || !field_ok(field)) return KG_ERR_BAD_ARG;
   if (n == 0) return KG_OK;
   KG_HIP(c, hipSetDevice(c->device));
   if (!out) return KG_ERR_BAD_ARG;
-  dim3 grid((unsigned)((n + 255) / 256));
-  if (field == KG_FR) hipLaunchKernelGGL(k_gen_scalars<FrParams>, grid, dim3(256), 0, c->stream, seed, start, n, out);
-  else hipLaunchKernelGGL(k_gen_scalars<FqParams>, grid, dim3(256), 0, c->stream, seed, start, n, out);
+  by_field(field, [&](auto p) { hipLaunchKernelGGL(k_gen_scalars<decltype(p)>, grid256(n), dim3(256), 0, c->stream, seed, start, n, out); });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }

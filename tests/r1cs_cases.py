@@ -31,7 +31,7 @@ def to_mont(vals, p):
 
 
 def random_shape(O, fd, m, nvars, seed, max_row=6):
-    """three random sparse matrices over z = (u | x | w) (the helper of tests/test_gpu_nova.py, restated, with the SHORT_ROW boundary): empty
+    """three random sparse matrices over z = (u | x | w) (tests/test_gpu_nova.py runs the cross term and the product on them as well): empty
     rows -- two of them empty in all three matrices --, repeated columns, coefficients +-1, a row of 200 entries, rows of exactly 48 and 49
     entries in one matrix only, rows of 254 entries at different constraints in A, B and C, one row of 5000 entries"""
     rng = np.random.default_rng(seed)

@@ -3,6 +3,8 @@
 import numpy as np
 import pytest
 
+from r1cs_cases import random_shape       # every row class of the row kernels, the SHORT_ROW boundary in one matrix only included
+
 pytestmark = pytest.mark.gpu
 SEED = 0x4B6F676172617368
 
@@ -13,28 +15,6 @@ def ctx():
     c = K.Context(0)
     yield c
     c.close()
-
-
-def random_shape(O, fd, m, nvars, seed, max_row=6):
-    """three random sparse matrices over z = (u | x | w) with empty rows, a long row and repeated columns"""
-    rng = np.random.default_rng(seed)
-    out = []
-    for j in range(3):
-        counts = rng.integers(0, max_row + 1, m)
-        counts[3 % m] = 0
-        if m > 10:
-            counts[7] = 200                              # one long row: past 48 entries a row gets a wave of its own (work list)
-        if m > 100:
-            counts[20 + j:60:7] = 254                    # range-check-like rows, at different constraints in A, B and C
-            counts[61] = 5000 if j == 1 else counts[61]
-        rp = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
-        col = rng.integers(0, nvars, int(rp[-1])).astype(np.uint64)
-        val = O.gen_scalars(fd, seed + 10 + j, 0, max(int(rp[-1]), 1))[: int(rp[-1])]
-        one = O.f_consts(fd)["r"]
-        val[::5] = one                                   # R1CS coefficients are mostly +-1
-        val[1::7] = O.f_neg(fd, one)
-        out.append((rp, col, np.ascontiguousarray(val)))
-    return out
 
 
 @pytest.mark.parametrize("fd,curve", [(0, 0), (1, 1)])
