@@ -2,7 +2,9 @@
 Every comparison is exact.  References: the oracle's Fft<Fr> (fft.rs:92-127) up to 2^16, the single-transform entry on a copy of the
 same data (checked against the oracle by tests/test_gpu_parity.py, test_gpu_large.py and test_gpu_ntt_big.py) at every size, and Python
 integers where the map is small enough to write out.  The sizes are the smallest that reach each code path: every one-step kernel
-(2^1..2^11), every column / row tile shape of the automatic two-step plans (2^12..2^21), a three-step plan whose middle step runs in
+(2^1..2^11), the column / row tile shapes the automatic two-step plans use (2^12..2^21: six of the eleven column and five of the nine
+two-step row shapes; no plan knob is set here, the shapes only a knob or a size from 2^22 up reaches are run by
+tests/test_gpu_ntt_shapes.py), a three-step plan whose middle step runs in
 place on two scratch slabs (2^22 x 2), a batch past the grid's y limit (65537 x 2^1) and one past a scratch group's edge (2049 x 2^12).
 Large inputs are generated on the device and compared there; only what is compared with a host reference is read back."""
 import ctypes as C

@@ -86,6 +86,85 @@ def test_plans_use_only_instantiated_shapes(nttlib):
                     assert bool(out[3 * i + 2]) == (i == c - 1)
 
 
+def _plan(nttlib, k, steps, tile):
+    """ht_ntt_plan as kg_ntt_plan reports it, [(log_m, log_tile)], and as the kernels it launches, {(log_m, log_tc, row)}"""
+    out = (C.c_int * 9)()
+    c = nttlib.ht_ntt_plan(k, steps, tile, out)
+    return [(out[3 * i], out[3 * i] + out[3 * i + 1]) for i in range(c)], {(out[3 * i], out[3 * i + 1], bool(out[3 * i + 2])) for i in range(c)}
+
+
+def test_shape_table_reaches_every_compiled_kernel(nttlib):
+    """the completeness gate of tests/ntt_shape_cases.py: every row's plan is as tabled, and the table's kernels together with those of the
+    automatic plans 2^1..2^21 (compared with the oracle on the device by the parity, large and batch tests) are every (shape, column / row)
+    pair ntt_tile.h instantiates.  A shape added to the lists without a row that reaches it fails here."""
+    import re
+    import ntt_shape_cases as T
+    hdr = open(os.path.join(ROOT, "kogarashi_amd", "csrc", "ntt_tile.h")).read()
+    shapes = lambda macro: {(int(m), int(tc)) for m, tc in re.findall(r"X\((\d+), (\d+)\)", re.search(r"#define %s\(X\)(.*)" % macro, hdr).group(1))}
+    both, col, row = shapes("KG_NTT_SHAPES"), shapes("KG_NTT_SHAPES_COL_ONLY"), shapes("KG_NTT_SHAPES_ROW_ONLY")
+    compiled = {(m, tc, False) for m, tc in both | col} | {(m, tc, True) for m, tc in both | row}
+    assert len(compiled) >= 31, "11 column and 20 row kernels when this gate was written: the shape lists were not parsed whole"
+    reached = set()
+    for k in list(range(1, 22)):
+        reached |= _plan(nttlib, k, 0, 0)[1]
+    for k in T.ONE_STEP:
+        assert _plan(nttlib, k, 0, 0)[0] == [(k, k)]
+    for env, k, plan, _ in T.ROWS:
+        got, kernels = _plan(nttlib, k, *T.knobs(env))
+        assert got == plan, (env, k, got)
+        assert kernels == T.kernels_of(plan)
+        reached |= kernels
+    assert reached <= compiled
+    missing = sorted(compiled - reached)
+    assert not missing, f"no table row or automatic plan up to 2^21 runs these (log_m, log_tc, row) kernels: {missing}"
+
+
+def _shape_rows(small):
+    import ntt_shape_cases as T
+    return [pytest.param(env, k, id=f"{T.env_id(env)}-{k}") for env, k, _, _ in T.ROWS if (k <= T.ORACLE_MAX_LOG) == small]
+
+
+def _run_tile(nttlib, k, steps, tile, inv, coset, checked, v):
+    d = np.ascontiguousarray(v.copy())
+    assert nttlib.ht_ntt_tile(int(checked), k, steps, tile, inv, coset, d.ctypes.data_as(C.c_void_p), None, None) == 0
+    return d
+
+
+@pytest.mark.parametrize("env,k", _shape_rows(True))
+def test_shape_table_rows(nttlib, oracle, env, k):
+    """the rows of tests/ntt_shape_cases.py up to 2^18 through the emulation, bound-tracking type: all four variants on the device test's
+    data and on every element p - 1.  A row that fails on the device and passes here fails in what the emulation cannot see (barriers,
+    wave privacy, LDS size, compilation, batched strides), not in the arithmetic."""
+    import ntt_shape_cases as T
+    steps, tile = T.knobs(env)
+    f = oracle.Fft(k)
+    for v in (oracle.gen_scalars(0, T.seed_of(k), 0, 1 << k), T.extreme_vectors(oracle, k)[0]):
+        for name, inv, coset in VARIANTS:
+            got = _run_tile(nttlib, k, steps, tile, inv, coset, True, v)
+            assert (got == getattr(f, name)(v, threads=8)).all(), (env, k, name)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("env,k", _shape_rows(False))
+def test_shape_table_rows_big(nttlib, oracle, env, k):
+    """the rows from 2^20 up: dft only, like test_big_tiles"""
+    import ntt_shape_cases as T
+    steps, tile = T.knobs(env)
+    v = oracle.gen_scalars(0, T.seed_of(k), 0, 1 << k)
+    assert (_run_tile(nttlib, k, steps, tile, 0, 0, False, v) == oracle.Fft(k).dft(v, threads=8)).all(), (env, k)
+
+
+@pytest.mark.parametrize("k", range(1, 12))
+def test_one_step_kernels_on_extreme_inputs(nttlib, oracle, k):
+    """the last table row on the host: every element p - 1, alternating p - 1 / 0 and a lone p - 1 through every one-step kernel,
+    bound-tracking type, all four variants"""
+    import ntt_shape_cases as T
+    f = oracle.Fft(k)
+    for v in T.extreme_vectors(oracle, k):
+        for name, inv, coset in VARIANTS:
+            assert (_run_tile(nttlib, k, 0, 0, inv, coset, True, v) == getattr(f, name)(v)).all(), (k, name)
+
+
 @pytest.mark.parametrize("k,steps,barriers", [(12, 0, 3), (18, 0, 3), (18, 3, 4), (20, 0, 5)])
 def test_wave_private_passes_replace_workgroup_barriers(nttlib, oracle, k, steps, barriers):
     """the synchronisation plan of ntt_tile.h: passes whose exchange stays inside a wave's 256-element block run without a
