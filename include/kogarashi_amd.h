@@ -193,6 +193,29 @@ int kg_commit(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_
  * a resident key. */
 int kg_commit_host_scalars(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* h_scalars,
                            size_t n, uint64_t* out_xy, uint8_t* out_inf);
+/* count MSMs of n pairs each against ONE base array, in one call: vector b's scalars are the n elements at
+ * d_scalars + b * stride * 4 words (stride in ELEMENTS, stride >= n; words between vectors are not read).
+ * d_out_xy: DEVICE, count x (8 | 16) words, affine; d_out_inf: DEVICE, count flags; the identity is (0, 1) + flag 1, as
+ * kg_fixed_base_mul writes it.  Point b is bit-identical to kg_commit(ctx, curve, d_bases, d_inf, d_scalars + b*stride*4, n, ...).
+ * Same preconditions on the bases as kg_msm (on the curve; KG_G2 in the r-torsion).
+ * For the lengths whose blocking call runs the short kernel with workgroups that convert the scalars themselves (by default
+ * 1 <= n <= 2048; kg_msm_set_small and KG_SMALL_GLV apply as they do to kg_commit; a forced window, kg_msm_set_window, leaves it) and
+ * for n == 0 (every output is the identity) the call is ENQUEUED on the context's stream and does not block -- the stream rule of
+ * kg_ntt_bn254_fr_batch: it runs behind whatever was enqueued, and the outputs are valid in stream order (the next kernel on the
+ * stream may read them) or after kg_ctx_sync.  A batch is one launch of the short kernel per launch group (vector in the grid's z
+ * dimension), one more for split windows, and a finish kernel that adds the window sums and normalises: no result crosses to the host.
+ * Groups (kg_commit_batch_plan) run one after another over one grow-only scratch of the context (at most 64 MiB per group).
+ * Outside those lengths the call MAY BLOCK: it runs count kg_commit calls and copies the points and flags to the device.
+ * count == 0: KG_OK, nothing is enqueued.  KG_ERR_BAD_ARG: a null ctx; null bases or scalars where a pair is read (n * count > 0); null
+ * outputs where a point is written (count > 0); stride < n; an unknown curve; a count * stride or byte size beyond size_t -- checked
+ * before anything is dereferenced. */
+int kg_commit_batch(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars,
+                    size_t n, size_t count, size_t stride, uint64_t* d_out_xy, uint8_t* d_out_inf);
+/* Pure function, no device, no context: returns the number of launch groups a batch is cut into and writes *per_launch
+ * (may be NULL) = min(65535, 64 MiB / scratch bytes of one vector); returns 0 with *per_launch = 0 when n is outside what the batched
+ * kernels take -- kg_commit_batch then runs count single kg_commit calls -- and for count == 0 or an unknown curve.  The process's
+ * settings decide (KG_SMALL_*); a context changed through kg_msm_set_small may cut its batches differently. */
+int kg_commit_batch_plan(int curve, size_t n, size_t count, size_t* per_launch);
 /* Per-GPU partial for the sharded commit: the un-normalised device result (raw window sums) is reduced on
  * the host to ONE affine partial; ranks exchange these (RCCL all_gather of 17/33 words) and add them with
  * kg_points_sum_affine.  See DESIGN.md "Multi-GPU". */

@@ -159,6 +159,25 @@ class PedersenCommitment:
         # the key is resident, m is a host slice: uploaded in index slices under the accumulations (kg_commit_host_scalars)
         return self.ctx.commit_host_scalars(self.cid, self._g.ptr, self._inf.ptr if self._inf else 0, m[:n], n)
 
+    def commit_batch(self, ms):
+        """Commitments of several vectors of ONE length against this key in one call (kg_commit_batch): ms is a list of equal-length
+        vectors or an array of shape (count, len, 4).  Returns (points, flags): arrays of shape (count, 8 | 16) and (count,); point b
+        equals commit(ms[b]) bit for bit, the identity is (0, 1) with flag 1."""
+        ms = np.ascontiguousarray(ms, dtype=np.uint64)
+        if ms.ndim == 2 and ms.shape[1] == 4:
+            raise ValueError("commit_batch takes a list of vectors or a (count, len, 4) array; use commit for one vector")
+        count = ms.shape[0]
+        ms = ms.reshape(count, -1, 4)
+        length = ms.shape[1]
+        n = min(length, self.len)
+        w = _LIMBS[self.cid]
+        if count == 0:
+            return np.zeros((0, w), dtype=np.uint64), np.zeros(0, dtype=np.uint8)
+        d_m = self.ctx.upload(ms)
+        d_xy, d_inf = self.ctx.empty((count, w)), self.ctx.empty((count,), dtype=np.uint8)
+        self.ctx.commit_batch(self.cid, self._g.ptr, self._inf.ptr if self._inf else 0, d_m.ptr, n, count, length, d_xy.ptr, d_inf.ptr)
+        return d_xy.numpy(), d_inf.numpy()      # (kg_memcpy_d2h follows the stream)
+
 
 class Prover:
     """groth16::Prover { params }: the CRS (groth16/src/params.rs:6-28) is uploaded once and stays resident.

@@ -388,6 +388,7 @@ void kg_ctx_destroy(kg_ctx* c) {
   if (c->side_stream) hipStreamSynchronize(c->side_stream);
   for (int i = 0; i < kg_ctx::RUN_SETS; ++i) { if (c->ws_run[i]) hipFree(c->ws_run[i]); if (c->ev_acc[i]) hipEventDestroy(c->ev_acc[i]); }
   for (int i = 0; i < kg_ctx::NSLOTS; ++i) if (c->ws_small[i]) hipFree(c->ws_small[i]);
+  if (c->ws_small_batch) hipFree(c->ws_small_batch);
   if (c->side_stream) hipStreamDestroy(c->side_stream);
   if (c->side2_stream) { hipStreamSynchronize(c->side2_stream); hipStreamDestroy(c->side2_stream); }
   if (c->ev_fork) hipEventDestroy(c->ev_fork);

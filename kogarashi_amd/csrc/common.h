@@ -83,6 +83,8 @@ struct kg_ctx {
   Slot slots[NSLOTS];
   void* ws_small[NSLOTS] = {};           // short-input MSM (msm_small.hip): plane points of a window split over several workgroups, per result slot (grow-only)
   size_t ws_small_bytes[NSLOTS] = {};
+  void* ws_small_batch = nullptr;        // batched short-input MSM (msm_small_batch.hip): window sums and plane points of one launch group (grow-only)
+  size_t ws_small_batch_bytes = 0;
   std::unique_ptr<kg::WorkerPool> workers;   // host worker threads (worker_pool.h), started on demand, alive until the context is destroyed
   std::shared_ptr<void> prover_jobs;     // groth16.hip: proofs in flight (kg_groth16_prove_begin / _end)
   size_t ticket_n[4] = {0, 0, 0, 0};

@@ -223,9 +223,20 @@ template <class F, class SP> struct SmEndo;
 template <class P, class SP> struct SmEndo<Fp<P>, SP> { static __device__ __forceinline__ void apply(Affine<Fp<P>>& pt) { sm_endo<P, SP>(pt); } };
 template <class G, class SP> struct SmEndo<Fp2<G>, SP> { static __device__ __forceinline__ void apply(Affine<Fp2<G>>& pt) { sm_endo<G, SP>(pt); } };
 
-template <class F, class SP, bool KT>
-__global__ void __launch_bounds__(SM_NT) k_msm_small(SmallArgs a) {
+// Which MSM a workgroup works on.  The kernels below read blockIdx.x (window) and blockIdx.y (bucket range) and nothing else of the grid; V
+// turns the kernel's argument into the SmallArgs of the workgroup's MSM.  SmOne: the argument is the one MSM of the launch (msm_small.hip).
+// The batched entry (msm_small_batch.hip) brings a V of its own whose argument carries per-vector strides and whose of() advances the
+// scalars, the window sums and the planes by the vector in the next grid dimension -- the second shell around the one body.  (A shared
+// __device__ body called from two __global__ shells costs k_msm_small<Fq | Fr, ., false> a VGPR: EXPERIMENTS.md Part T.)
+struct SmOne {
+  using Args = SmallArgs;
+  static __device__ __forceinline__ const SmallArgs& of(const SmallArgs& a) { return a; }
+};
+
+template <class F, class SP, bool KT, class V = SmOne>
+__global__ void __launch_bounds__(SM_NT) k_msm_small(typename V::Args av) {
   extern __shared__ uint32_t lds[];
+  const SmallArgs& a = V::of(av);
   constexpr int NW = PointIO<F>::NW;
   const uint32_t tid = threadIdx.x, qd = tid >> 2;
   const int c = a.c, W = a.W, r = a.r;
@@ -499,9 +510,10 @@ __global__ void __launch_bounds__(SM_NT) k_msm_small(SmallArgs a) {
 // Second launch of a split window (its 2^(c-1) buckets dealt to NB workgroups, bucket b to workgroup b mod NB): the plane of bucket bit
 // h < log2 NB is the sum of the totals A_j of the workgroups whose index j has bit h set, the plane of bit log2 NB + l the sum of the
 // workgroups' local planes l, the total the sum of all A_j.  LDS: c planes x NB items; a tree of cooperative additions along the ranges, then the combine of the fused kernel.
-template <class F>
-__global__ void __launch_bounds__(SM_NT) k_msm_small_combine(SmallArgs a) {
+template <class F, class V = SmOne>
+__global__ void __launch_bounds__(SM_NT) k_msm_small_combine(typename V::Args av) {
   extern __shared__ uint32_t lds[];
+  const SmallArgs& a = V::of(av);
   constexpr int NW = PointIO<F>::NW;
   const uint32_t tid = threadIdx.x, w = blockIdx.x, qd = tid >> 2;
   const int c = a.c, r = a.r;

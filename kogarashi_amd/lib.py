@@ -33,6 +33,7 @@ EXPORTS = [
     "kg_msm_set_small", "kg_ctx_worker_threads", "kg_ctx_queue_placement2", "kg_ctx_trim",
     "kg_points_check", "kg_groth16_crs_check", "kg_r1cs_check",
     "kg_ntt_bn254_fr_batch", "kg_fr_divide_by_z_on_coset_batch", "kg_ntt_batch_plan",
+    "kg_commit_batch", "kg_commit_batch_plan",
 ]
 
 
@@ -103,6 +104,10 @@ def load():
         _lib.kg_fr_divide_by_z_on_coset_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t]
         _lib.kg_ntt_batch_plan.restype = C.c_int
         _lib.kg_ntt_batch_plan.argtypes = [C.c_uint32, C.c_size_t, C.POINTER(C.c_size_t)]
+        _lib.kg_commit_batch.restype = C.c_int
+        _lib.kg_commit_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+        _lib.kg_commit_batch_plan.restype = C.c_int
+        _lib.kg_commit_batch_plan.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
     return _lib
 
 
@@ -133,6 +138,15 @@ def ntt_batch_plan(log_n: int, count: int) -> tuple[int, int]:
     carries); (0, 0) for log_n outside 1..28, 0 groups for count == 0 (no device needed)"""
     per = C.c_size_t(0)
     groups = int(load().kg_ntt_batch_plan(C.c_uint32(log_n), C.c_size_t(count), C.byref(per)))
+    return groups, int(per.value)
+
+
+def commit_batch_plan(curve: int, n: int, count: int) -> tuple[int, int]:
+    """kg_commit_batch_plan: (launch groups a batch of `count` MSMs of n pairs is cut into, most vectors one group carries); (0, 0) where
+    kg_commit_batch runs single kg_commit calls instead (n beyond the batched kernels' lengths), for count == 0 and for an unknown curve
+    (no device needed)"""
+    per = C.c_size_t(0)
+    groups = int(load().kg_commit_batch_plan(int(curve), C.c_size_t(n), C.c_size_t(count), C.byref(per)))
     return groups, int(per.value)
 
 
@@ -356,6 +370,13 @@ class Context:
         oi = C.c_uint8(0)
         self._chk(self._lib.kg_commit(self._h, curve, _vp(bases), _vp(inf), _vp(scalars), C.c_size_t(n), xy.ctypes.data_as(C.c_void_p), C.byref(oi)), "kg_commit")
         return xy, int(oi.value)
+
+    def commit_batch(self, curve: int, bases: int, inf: int, scalars: int, n: int, count: int, stride: int, out_xy: int, out_inf: int):
+        """kg_commit_batch: count MSMs of n pairs against ONE base array; vector b's scalars begin at element b * stride of `scalars`
+        (stride >= n).  Everything is a device pointer: out_xy takes count affine points (8 | 16 words), out_inf count flags, valid in
+        stream order or after sync().  Does not block for n up to 2048 (the batched kernels); beyond, it runs count commit() calls."""
+        self._chk(self._lib.kg_commit_batch(self._h, int(curve), _vp(bases), _vp(inf), _vp(scalars), C.c_size_t(n), C.c_size_t(count), C.c_size_t(stride),
+                                            _vp(out_xy), _vp(out_inf)), "kg_commit_batch")
 
     def points_sum_affine(self, curve: int, pts: np.ndarray, inf: np.ndarray):
         pts = np.ascontiguousarray(pts, dtype=np.uint64)
