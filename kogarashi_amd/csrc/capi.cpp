@@ -15,7 +15,7 @@ namespace kg {
 void sync_all(kg_ctx* c) {
   hipStreamSynchronize(c->stream);
   if (c->own_stream && c->own_stream != c->stream) hipStreamSynchronize(c->own_stream);
-  for (hipStream_t s : {c->sort_stream, c->side_stream, c->side2_stream, c->up_stream})
+  for (hipStream_t s : {c->sort_stream.h, c->side_stream.h, c->side2_stream.h, c->up_stream.h})
     if (s) hipStreamSynchronize(s);
   for (hipStream_t s : c->acc_stream)
     if (s) hipStreamSynchronize(s);
@@ -29,24 +29,33 @@ static size_t pool_class(size_t bytes) {
 // Process-wide bookkeeping of the pool: the live contexts (a device that runs out of memory gets the kept blocks of EVERY context on it
 // back, not only the caller's) and the blocks kg_malloc has handed out, by address -> (owner, size class): kg_free through another
 // context than the allocating one still finds the block (it is released, not kept), and a stale entry cannot outlive its address.
+// g_pool_mu guards them and every context's pool_free / pool_cached.  hipFree waits for the device, so nothing is released under the
+// lock: the blocks are taken out of the pool under it and released after it.
 static std::mutex g_pool_mu;
 static std::vector<kg_ctx*> g_ctxs;
 static std::unordered_map<void*, std::pair<kg_ctx*, size_t>> g_live;
-static void pool_trim_locked(kg_ctx* c) {                  // g_pool_mu held
-  for (auto& kv : c->pool_free) hipFree(kv.second);
+static size_t pool_take_locked(kg_ctx* c, std::vector<void*>& out) {      // g_pool_mu held; returns the bytes taken
+  const size_t bytes = c->pool_cached;
+  for (auto& kv : c->pool_free) out.push_back(kv.second);
   c->pool_free.clear();
   c->pool_cached = 0;
+  return bytes;
 }
 void pool_trim(kg_ctx* c) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
-  pool_trim_locked(c);
+  std::vector<void*> blocks;
+  { std::lock_guard<std::mutex> lk(g_pool_mu); pool_take_locked(c, blocks); }
+  for (void* b : blocks) hipFree(b);
 }
 // the kept blocks of every context of the device (a kept block is idle by construction: its context was drained when it was kept)
 static size_t pool_trim_device(int device) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
+  std::vector<void*> blocks;
   size_t freed = 0;
-  for (kg_ctx* o : g_ctxs)
-    if (o->device == device) { freed += o->pool_cached; pool_trim_locked(o); }
+  {
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    for (kg_ctx* o : g_ctxs)
+      if (o->device == device) freed += pool_take_locked(o, blocks);
+  }
+  for (void* b : blocks) hipFree(b);
   return freed;
 }
 hipError_t dev_alloc(kg_ctx* c, void** p, size_t bytes) {
@@ -57,15 +66,6 @@ hipError_t dev_alloc(kg_ctx* c, void** p, size_t bytes) {
     if (pool_trim_device(c->device)) e = hipMalloc(p, bytes);
   }
   return e;
-}
-int ensure_ws_sort(kg_ctx* c, int set, size_t bytes) {
-  if (bytes <= c->ws_sort_bytes[set]) return KG_OK;
-  if (c->ws_sort[set]) { sync_all(c); hipFree(c->ws_sort[set]); c->ws_sort[set] = nullptr; c->ws_sort_bytes[set] = 0; }
-  size_t want = bytes + bytes / 8;
-  hipError_t e = dev_alloc(c, &c->ws_sort[set], want);
-  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, "workspace allocation", e);
-  c->ws_sort_bytes[set] = want;
-  return KG_OK;
 }
 // The context's queues (main, scalar, two reduction queues, an upload queue for kg_msm_host) should each own a hardware queue:
 // the runtime multiplexes HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, shared with whatever else the process
@@ -120,22 +120,19 @@ static int place_queues(kg_ctx* c) {
   // never saw "j and j + 4" among eight candidates), so LEAD streams are created and launched on in front of the eight candidates; they
   // take part in the probe and are released after it (tests/test_gpu_parity.py test_service_queues_are_placed_off_the_main_queues_pipe).
   constexpr int LEAD = 4, NC = 8;
-  hipStream_t all[LEAD + NC] = {};
-  hipStream_t* const cand = all + LEAD;
+  Queue all[LEAD + NC];                                 // released on return: the lead streams and the candidates nobody took
+  Queue* const cand = all + LEAD;
   hipError_t e = hipSuccess;
-  for (int j = 0; j < LEAD + NC && e == hipSuccess; ++j) e = create_stream(c, &all[j], true);
-  if (e != hipSuccess) {                                // nothing is kept: the candidates made so far are released, a later call tries again
-    for (int j = 0; j < LEAD + NC; ++j) if (all[j]) hipStreamDestroy(all[j]);
-    return set_err(c, KG_ERR_HIP, "queue creation", e);
-  }
+  for (int j = 0; j < LEAD + NC && e == hipSuccess; ++j) e = create_stream(c, &all[j].h, true);
+  if (e != hipSuccess) return set_err(c, KG_ERR_HIP, "queue creation", e);      // nothing is kept: a later call tries again
   int cls[NC];
   for (int j = 0; j < NC; ++j) cls[j] = -1;
   const bool enabled = c->tune.queue_placement != 0;
   bool ok = enabled;
   if (ok) {
-    hipEvent_t ev_s = nullptr, ev_a = nullptr, ev_b[NC] = {};
-    ok = hipEventCreate(&ev_s) == hipSuccess && hipEventCreate(&ev_a) == hipSuccess;
-    for (int j = 0; j < NC && ok; ++j) ok = hipEventCreate(&ev_b[j]) == hipSuccess;
+    Event ev_s, ev_a, ev_b[NC];                         // (with timing)
+    ok = hipEventCreate(&ev_s.h) == hipSuccess && hipEventCreate(&ev_a.h) == hipSuccess;
+    for (int j = 0; j < NC && ok; ++j) ok = hipEventCreate(&ev_b[j].h) == hipSuccess;
     ok = ok && hipFuncSetAttribute((const void*)k_probe_busy, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
     bool shares[NC] = {};
     int j0 = -1;
@@ -169,97 +166,39 @@ static int place_queues(kg_ctx* c) {
       for (int j = 0; j < NC && j0 >= 0; ++j) if (shares[j] != ((j - j0) % 4 == 0)) j0 = -1;
     }
     (void)hipGetLastError();
-    if (ev_s) hipEventDestroy(ev_s);
-    if (ev_a) hipEventDestroy(ev_a);
-    for (int j = 0; j < NC; ++j) if (ev_b[j]) hipEventDestroy(ev_b[j]);
     ok = ok && j0 >= 0;
     if (ok) for (int j = 0; j < NC; ++j) cls[j] = ((j - j0) % 4 + 4) % 4;      // 0: the main queue's pipe
     c->placement = ok ? 1 + j0 : -1;
   } else c->placement = 0;
   auto take = [&](int want) -> hipStream_t {                // first unused candidate of the class (any class when the probe gave no picture)
     for (int j = 0; j < NC; ++j)
-      if (cand[j] && (cls[j] == want || !ok)) { hipStream_t t = cand[j]; cand[j] = nullptr; return t; }
-    for (int j = 0; j < NC; ++j) if (cand[j]) { hipStream_t t = cand[j]; cand[j] = nullptr; return t; }
+      if (cand[j] && (cls[j] == want || !ok)) { hipStream_t t = cand[j]; cand[j].h = nullptr; return t; }
+    for (int j = 0; j < NC; ++j) if (cand[j]) { hipStream_t t = cand[j]; cand[j].h = nullptr; return t; }
     return nullptr;
   };
-  c->sort_stream = take(1);
-  c->side_stream = take(2);
-  c->side2_stream = take(3);
-  c->acc_stream[1] = take(0);
-  c->up_stream = take(3);                                 // kg_msm_host's upload queue: copies only
-  for (int j = 0; j < LEAD + NC; ++j) if (all[j]) hipStreamDestroy(all[j]);      // the lead streams and the candidates nobody took
+  c->sort_stream.h = take(1);
+  c->side_stream.h = take(2);
+  c->side2_stream.h = take(3);
+  c->acc_stream[1].h = take(0);
+  c->up_stream.h = take(3);                               // kg_msm_host's upload queue: copies only
   c->queues_placed = true;                                // only now: every queue the context uses exists
   return KG_OK;
 }
 int make_sort_stream(kg_ctx* c) {
   if (c->sort_events) return KG_OK;
   KG_TRY(place_queues(c));
-  hipError_t e = c->sort_stream ? hipSuccess : create_stream(c, &c->sort_stream, true);
+  hipError_t e = c->sort_stream ? hipSuccess : create_stream(c, &c->sort_stream.h, true);
   if (e != hipSuccess) return set_err(c, KG_ERR_HIP, "scalar-queue creation", e);
-  for (int i = 0; i < 2; ++i) {
-    for (int g = 0; g < kg_ctx::MAX_GROUPS; ++g)
-      if ((e = hipEventCreateWithFlags(&c->ev_sorted[i][g], hipEventDisableTiming)) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
-    for (int j = 0; j < kg_ctx::IDLE_EVS; ++j)
-      if ((e = hipEventCreateWithFlags(&c->ev_ws_idle[i][j], hipEventDisableTiming)) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
-  }
-  if ((e = hipEventCreateWithFlags(&c->ev_bases, hipEventDisableTiming)) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
-  if ((e = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming)) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
-  if ((e = hipEventCreateWithFlags(&c->ev_pb, hipEventDisableTiming)) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
-  if ((e = hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming)) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
-  for (int g = 0; g < kg_ctx::MAX_GROUPS; ++g)
-    if ((e = hipEventCreateWithFlags(&c->ev_info[g], hipEventDisableTiming)) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
+  e = create_events({c->ev_sorted[0], c->ev_sorted[1], c->ev_ws_idle[0], c->ev_ws_idle[1], c->ev_bases, c->ev_order, c->ev_pb, c->ev_prep, c->ev_info});
+  if (e != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation", e);
   c->sort_events = true;
-  return KG_OK;
-}
-int ensure_ws_vec(kg_ctx* c, size_t bytes) {
-  if (bytes <= c->ws_vec_bytes) return KG_OK;
-  if (c->ws_vec) { sync_all(c); hipFree(c->ws_vec); c->ws_vec = nullptr; c->ws_vec_bytes = 0; }
-  hipError_t e = dev_alloc(c, &c->ws_vec, bytes);
-  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, "workspace allocation", e);
-  c->ws_vec_bytes = bytes;
-  return KG_OK;
-}
-int ensure_ws2(kg_ctx* c, size_t bytes) {
-  if (bytes <= c->ws2_bytes) return KG_OK;
-  if (c->ws2) { sync_all(c); hipFree(c->ws2); c->ws2 = nullptr; c->ws2_bytes = 0; }
-  hipError_t e = dev_alloc(c, &c->ws2, bytes);
-  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, "ntt buffer allocation", e);
-  c->ws2_bytes = bytes;
-  return KG_OK;
-}
-int ensure_ws3(kg_ctx* c, int which, size_t bytes) {
-  if (bytes <= c->ws3_bytes[which]) return KG_OK;
-  if (c->ws3[which]) { sync_all(c); hipFree(c->ws3[which]); c->ws3[which] = nullptr; c->ws3_bytes[which] = 0; }
-  hipError_t e = dev_alloc(c, &c->ws3[which], bytes);
-  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, "prover buffer allocation", e);
-  c->ws3_bytes[which] = bytes;
-  return KG_OK;
-}
-int ensure_ws_run(kg_ctx* c, int which, size_t bytes) {
-  if (bytes <= c->ws_run_bytes[which]) return KG_OK;
-  if (c->ws_run[which]) {
-    sync_all(c);
-    hipFree(c->ws_run[which]);
-    c->ws_run[which] = nullptr; c->ws_run_bytes[which] = 0;
-  }
-  size_t want = bytes + bytes / 8;
-  hipError_t e = dev_alloc(c, &c->ws_run[which], want);
-  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, "msm run-space allocation", e);
-  c->ws_run_bytes[which] = want;
   return KG_OK;
 }
 int ensure_slot(kg_ctx* c, int slot, size_t bytes) {
   if (slot < 0 || slot >= kg_ctx::NSLOTS) return set_err(c, KG_ERR_BAD_ARG, "bad result slot");
   kg_ctx::Slot& s = c->slots[slot];
-  if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation");
-  if (bytes <= s.bytes) return KG_OK;
-  if (s.host) hipHostFree(s.host);
-  s.host = nullptr; s.host_dev = nullptr; s.bytes = 0;
-  hipError_t e = hipHostMalloc(&s.host, bytes, hipHostMallocDefault);
-  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, "pinned slot allocation", e);
-  if ((e = hipHostGetDevicePointer(&s.host_dev, s.host, 0)) != hipSuccess) return set_err(c, KG_ERR_HIP, "pinned slot device view", e);
-  s.bytes = bytes;
-  return KG_OK;
+  if (create_events({s.done}) != hipSuccess) return set_err(c, KG_ERR_HIP, "event creation");
+  return s.host.ensure(PinMem{c, "pinned slot"}, bytes);
 }
 // The side stream carries the latency-bound bucket reductions of MSM i under the sort / accumulation of MSM i+1.
 // (A lowest-priority stream was measured and made no difference: the two queues do not compete for issue slots.)
@@ -267,28 +206,17 @@ int make_side_stream(kg_ctx* c) {
   // (stream priorities were measured, high and low, for the prover and the MSM pipeline: no gain either way)
   if (c->side_stream && c->side2_stream) return KG_OK;
   KG_TRY(place_queues(c));
-  hipError_t e = c->side_stream ? hipSuccess : create_stream(c, &c->side_stream, true);
+  hipError_t e = c->side_stream ? hipSuccess : create_stream(c, &c->side_stream.h, true);
   if (e != hipSuccess) return set_err(c, KG_ERR_HIP, "side stream creation", e);
-  e = c->side2_stream ? hipSuccess : create_stream(c, &c->side2_stream, true);
+  e = c->side2_stream ? hipSuccess : create_stream(c, &c->side2_stream.h, true);
   if (e != hipSuccess) return set_err(c, KG_ERR_HIP, "side stream creation", e);
-  return KG_OK;
-}
-int ensure_pinned(kg_ctx* c, size_t bytes) {
-  if (bytes <= c->h_pinned_bytes) return KG_OK;
-  if (c->h_pinned) hipHostFree(c->h_pinned);
-  c->h_pinned = nullptr; c->h_pinned_bytes = 0;
-  hipError_t e = hipHostMalloc(&c->h_pinned, bytes, hipHostMallocDefault);
-  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, "pinned staging allocation", e);
-  if ((e = hipHostGetDevicePointer(&c->h_pinned_dev, c->h_pinned, 0)) != hipSuccess) return set_err(c, KG_ERR_HIP, "pinned staging device view", e);
-  c->h_pinned_bytes = bytes;
   return KG_OK;
 }
 
 static hipEvent_t next_event(kg_ctx* c) {
   if (c->event_next == c->event_pool.size()) {
-    hipEvent_t e;
-    hipEventCreate(&e);
-    c->event_pool.push_back(e);
+    c->event_pool.emplace_back();
+    hipEventCreate(&c->event_pool.back().h);
   }
   return c->event_pool[c->event_next++];
 }
@@ -358,7 +286,7 @@ int kg_ctx_create(int device, kg_ctx** out) {
   kg_ctx* c = new kg_ctx();
   c->device = device;
   c->tune = tuning();
-  if (create_stream(c, &c->own_stream, false) != hipSuccess) { delete c; return KG_ERR_HIP; }
+  if (create_stream(c, &c->own_stream.h, false) != hipSuccess) { delete c; return KG_ERR_HIP; }
   c->stream = c->own_stream;
   { std::lock_guard<std::mutex> lk(g_pool_mu); g_ctxs.push_back(c); }
   *out = c;
@@ -372,51 +300,17 @@ void kg_ctx_destroy(kg_ctx* c) {
   c->prover_jobs.reset();                             // joins the worker threads of proofs still in flight
   for (auto& f : c->ticket_fut) if (f.valid()) f.wait();      // and of MSM tickets begun and never ended
   c->workers.reset();                                 // the worker threads are idle now: joined here, before what they work on is released
-  hipStreamSynchronize(c->stream);
+  sync_all(c);
   tw_cache_free(c);
-  for (int i = 0; i < 2; ++i) {
-    if (c->ws_sort[i]) hipFree(c->ws_sort[i]);
-    for (int g = 0; g < kg_ctx::MAX_GROUPS; ++g) if (c->ev_sorted[i][g]) hipEventDestroy(c->ev_sorted[i][g]);
-    for (int j = 0; j < kg_ctx::IDLE_EVS; ++j) if (c->ev_ws_idle[i][j]) hipEventDestroy(c->ev_ws_idle[i][j]);
-  }
-  if (c->ev_bases) hipEventDestroy(c->ev_bases);
-  if (c->ev_order) hipEventDestroy(c->ev_order);
-  if (c->sort_stream) { hipStreamSynchronize(c->sort_stream); hipStreamDestroy(c->sort_stream); }
-  if (c->ws2) hipFree(c->ws2);
-  if (c->ws_vec) hipFree(c->ws_vec);
-  for (int i = 0; i < 2; ++i) if (c->ws3[i]) hipFree(c->ws3[i]);
-  if (c->side_stream) hipStreamSynchronize(c->side_stream);
-  for (int i = 0; i < kg_ctx::RUN_SETS; ++i) { if (c->ws_run[i]) hipFree(c->ws_run[i]); if (c->ev_acc[i]) hipEventDestroy(c->ev_acc[i]); }
-  for (int i = 0; i < kg_ctx::NSLOTS; ++i) if (c->ws_small[i]) hipFree(c->ws_small[i]);
-  if (c->ws_small_batch) hipFree(c->ws_small_batch);
-  if (c->side_stream) hipStreamDestroy(c->side_stream);
-  if (c->side2_stream) { hipStreamSynchronize(c->side2_stream); hipStreamDestroy(c->side2_stream); }
-  if (c->ev_fork) hipEventDestroy(c->ev_fork);
-  for (int i = 0; i < 3; ++i) if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]);
-  for (int g = 0; g < kg_ctx::MAX_GROUPS; ++g) {
-    if (c->ev_info[g]) hipEventDestroy(c->ev_info[g]);
-    if (c->acc_stream[g]) { hipStreamSynchronize(c->acc_stream[g]); hipStreamDestroy(c->acc_stream[g]); }
-  }
-  if (c->ev_pb) hipEventDestroy(c->ev_pb);
-  if (c->ev_prep) hipEventDestroy(c->ev_prep);
+  std::vector<void*> kept;
   {                                                      // (blocks the host still holds stay allocated, as before the pool: they are the host's -- released through any other context, or with the process)
     std::lock_guard<std::mutex> lk(g_pool_mu);
-    pool_trim_locked(c);
+    pool_take_locked(c, kept);
     for (auto it = g_ctxs.begin(); it != g_ctxs.end(); ++it) if (*it == c) { g_ctxs.erase(it); break; }
     for (auto& kv : g_live) if (kv.second.first == c) kv.second.first = nullptr;
   }
-  if (c->ws_pb) hipFree(c->ws_pb);
-  for (auto& sl : c->slots) { if (sl.host) hipHostFree(sl.host); if (sl.done) hipEventDestroy(sl.done); }
-  if (c->h_pinned) hipHostFree(c->h_pinned);
-  for (void* b : c->up_buf) if (b) hipFree(b);
-  for (uint32_t* t : c->fb_table) if (t) hipFree(t);
-  if (c->fb_tmp) hipFree(c->fb_tmp);
-  if (c->ws_points) hipFree(c->ws_points);
-  if (c->up_stream) { hipStreamSynchronize(c->up_stream); hipStreamDestroy(c->up_stream); }
-  for (int i = 0; i < kg_ctx::UP_SLICES; ++i) { if (c->ev_up_s[i]) hipEventDestroy(c->ev_up_s[i]); if (c->ev_up_b[i]) hipEventDestroy(c->ev_up_b[i]); }
-  for (auto& r : c->registered) { hipFree(r.packed); if (r.table) hipFree(r.table); }
-  for (hipEvent_t e : c->event_pool) hipEventDestroy(e);
-  if (c->own_stream) hipStreamDestroy(c->own_stream);
+  for (void* b : kept) hipFree(b);
+  // everything else the context holds releases itself, buffers and events before the queues (kg_ctx's member order)
   delete c;
 }
 
@@ -438,7 +332,7 @@ int kg_ctx_sync(kg_ctx* c) {
   if (!c) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
   KG_HIP(c, hipStreamSynchronize(c->stream));
-  for (hipStream_t s : {c->sort_stream, c->side_stream, c->side2_stream})
+  for (hipStream_t s : {c->sort_stream.h, c->side_stream.h, c->side2_stream.h})
     if (s) KG_HIP(c, hipStreamSynchronize(s));
   for (hipStream_t s : c->acc_stream)
     if (s) KG_HIP(c, hipStreamSynchronize(s));
@@ -499,7 +393,10 @@ int kg_mem_info(kg_ctx* c, size_t* free_bytes, size_t* total_bytes) {
   KG_HIP(c, hipSetDevice(c->device));
   size_t f = 0, t = 0;
   KG_HIP(c, hipMemGetInfo(&f, &t));
-  if (free_bytes) *free_bytes = f + c->pool_cached;        // kept blocks are released on demand: they count as free
+  if (free_bytes) {
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    *free_bytes = f + c->pool_cached;                      // kept blocks are released on demand: they count as free
+  }
   if (total_bytes) *total_bytes = t;
   return KG_OK;
 }
@@ -521,13 +418,19 @@ int kg_free(kg_ctx* c, void* p) {
   // drained its queues for them): released
   if (!ours || owner != c) { KG_HIP(c, hipFree(p)); return KG_OK; }
   const size_t cap = (size_t)(c->tune.pool_mb > 0 ? c->tune.pool_mb : 0) << 20;
-  if (c->pool_cached + cls <= cap) {
-    // hipFree waits for the device; a kept block must be just as safe to hand out again: nothing of this context may still use it
+  const auto fits = [&] { return c->pool_cached + cls <= cap; };      // g_pool_mu held
+  bool room;
+  { std::lock_guard<std::mutex> lk(g_pool_mu); room = fits(); }
+  if (room) {
+    // hipFree waits for the device; a kept block must be just as safe to hand out again: nothing of this context may still use it.
+    // The drain happens outside the lock, so the room is checked again with the insert (another thread may have filled the pool).
     sync_all(c);
     std::lock_guard<std::mutex> lk(g_pool_mu);
-    c->pool_free.emplace(cls, p);
-    c->pool_cached += cls;
-    return KG_OK;
+    if (fits()) {
+      c->pool_free.emplace(cls, p);
+      c->pool_cached += cls;
+      return KG_OK;
+    }
   }
   KG_HIP(c, hipFree(p));
   return KG_OK;

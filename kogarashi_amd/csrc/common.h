@@ -12,17 +12,84 @@
 #include <vector>
 #include <thread>
 #include <new>
+#include <initializer_list>
 #include "../../include/kogarashi_amd.h"
 #include "curve.h"
 #include "tuning.h"
 #include "worker_pool.h"
+#include "grow_buf.h"
 
 struct kg_tw_cache;   // ntt.hip
+struct kg_ctx;
 
+namespace kg {
+// ---- owners: what the context (or a call) holds releases itself ("Who owns what") ------------------------------------------
+// Device memory of a context's work spaces: dev_alloc / hipFree, and every queue of the context is drained (sync_all) before a block
+// goes.  what: the text kg_last_error carries with KG_ERR_OOM when the device refuses.
+struct DevMem {
+  kg_ctx* c = nullptr;
+  const char* what = "device allocation";
+  static constexpr bool drains = true;
+  int alloc(void** p, size_t bytes);
+  void drain_before_release();
+  void release(void* p) { (void)hipFree(p); }
+};
+// Pinned host memory and its device view (kernels write results straight into it).  what: "<what> allocation" (KG_ERR_OOM) /
+// "<what> device view" (KG_ERR_HIP).  Nothing is drained: a pinned buffer grows only between the calls that use it.
+struct PinMem {
+  kg_ctx* c = nullptr;
+  const char* what = "pinned";
+  void* dev = nullptr;
+  static constexpr bool drains = false;
+  int alloc(void** p, size_t bytes);
+  void release(void* p) { (void)hipHostFree(p); dev = nullptr; }
+};
+using DevBuf = GrowBuf<DevMem>;
+using PinBuf = GrowBuf<PinMem>;
+struct Event {
+  hipEvent_t h = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { if (h) (void)hipEventDestroy(h); }
+  operator hipEvent_t() const { return h; }
+};
+struct Queue {                           // a stream the library created: drained, then destroyed
+  hipStream_t h = nullptr;
+  Queue() = default;
+  Queue(const Queue&) = delete;
+  Queue& operator=(const Queue&) = delete;
+  ~Queue() { if (h) { (void)hipStreamSynchronize(h); (void)hipStreamDestroy(h); } }
+  operator hipStream_t() const { return h; }
+};
+// Creates those events of the list that do not exist yet (no timing); the first failure is returned.  An item is one event or an array.
+struct EventRun {
+  Event* p; size_t n;
+  EventRun(Event& e) : p(&e), n(1) {}
+  template <size_t N> EventRun(Event (&a)[N]) : p(a), n(N) {}
+};
+inline hipError_t create_events(std::initializer_list<EventRun> runs) {
+  for (const EventRun& r : runs)
+    for (size_t i = 0; i < r.n; ++i)
+      if (!r.p[i].h)
+        if (hipError_t e = hipEventCreateWithFlags(&r.p[i].h, hipEventDisableTiming); e != hipSuccess) return e;
+  return hipSuccess;
+}
+}  // namespace kg
+
+// Members are destroyed in reverse order of declaration: the queues come first, so that they outlive the buffers and events used on them.
 struct kg_ctx {
   int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;          // stream every launch goes to
+  kg::Queue own_stream;
+  hipStream_t stream = nullptr;          // stream every launch goes to (own_stream, or the caller's: kg_ctx_set_stream)
+  kg::Queue sort_stream;                 // scalar-side queue (prep_scalars, sort, task bookkeeping); == stream when no overlap is possible
+  static constexpr int MAX_GROUPS = 4;
+  kg::Queue acc_stream[MAX_GROUPS];      // accumulation queues of window groups 1.. (group 0: the main queue), so that the
+                                         // groups' launches share the chip instead of draining one after the other
+  kg::Queue side_stream;                 // bucket reduction of MSM i overlaps the accumulation of MSM i+1
+  kg::Queue side2_stream;                // second reduction queue (odd slots): a slow G2 reduction does not hold up the next MSM's
+  kg::Queue up_stream;                   // kg_msm_host: the upload queue
   std::string last_error;
   kg_tuning tune;                        // the knob table (tuning.h): the process-wide values at creation
   int msm_window = 0;                    // 0 = auto
@@ -31,29 +98,23 @@ struct kg_ctx {
   // grow-only scratch
   // MSM scalar-side space (sorted digit lists, task tables), two sets used in turn: the sort of MSM i+1 runs on the scalar
   // queue while the accumulation of MSM i still reads the other set
-  void* ws_sort[2] = {nullptr, nullptr};
-  size_t ws_sort_bytes[2] = {0, 0};
+  kg::DevBuf ws_sort[2];
   unsigned sort_seq = 0;
   bool queues_placed = false, sort_events = false;   // capi.cpp place_queues: the service queues were created (and dealt over the compute pipes)
   int placement = 0;                     // 0: not probed; 1 + j: the probe's picture (candidate j shares the main queue's pipe); -1: no clear picture, creation order
-  hipStream_t sort_stream = nullptr;     // scalar-side queue (prep_scalars, sort, task bookkeeping); == stream when no overlap is possible
   // A blocking MSM pipelines against itself by WINDOW GROUPS (msm.hip, kg_msm): the scalars are converted once, then the
   // windows are sorted, accumulated and reduced group by group, top windows first -- group g+1 is sorted under group g's
   // accumulation, group g is reduced under group g+1's accumulation, and the host's double-and-add chain starts with the top
   // group's sums while the lower groups are still on the device.  No extra work (index slices add reduction tails).
-  static constexpr int MAX_GROUPS = 4;
-  hipEvent_t ev_sorted[2][MAX_GROUPS] = {};         // sort of the set's window group complete (recorded on the scalar queue)
-  hipStream_t acc_stream[MAX_GROUPS] = {};          // accumulation queues of window groups 1.. (group 0: the main queue), so that the
-                                                    // groups' launches share the chip instead of draining one after the other
-  void* ws_pb = nullptr;                            // per-call resident form of the bases, shared by the window groups of one MSM
-  size_t ws_pb_bytes = 0;
-  hipEvent_t ev_pb = nullptr;                       // its conversion complete
-  hipEvent_t ev_prep = nullptr;                     // scalar conversion on the main queue complete (the scalar queue's sorts follow it)
+  kg::Event ev_sorted[2][MAX_GROUPS];               // sort of the set's window group complete (recorded on the scalar queue)
+  kg::DevBuf ws_pb;                                 // per-call resident form of the bases, shared by the window groups of one MSM
+  kg::Event ev_pb;                                  // its conversion complete
+  kg::Event ev_prep;                                // scalar conversion on the main queue complete (the scalar queue's sorts follow it)
   static constexpr int IDLE_EVS = 8;                // readers of one set whose completion the next sort into it waits for
-  hipEvent_t ev_ws_idle[2][IDLE_EVS] = {};          // a bucket gather that read the set's level tables is complete (reduction queues)
+  kg::Event ev_ws_idle[2][IDLE_EVS];                // a bucket gather that read the set's level tables is complete (reduction queues)
   int ws_idle_n[2] = {0, 0};
-  hipEvent_t ev_bases = nullptr;                    // per-call base conversion on the scalar queue complete
-  hipEvent_t ev_order = nullptr;         // stream-order hand-over main -> scalar queue
+  kg::Event ev_bases;                               // per-call base conversion on the scalar queue complete
+  kg::Event ev_order;                    // stream-order hand-over main -> scalar queue
   unsigned small_glv_off = 0;            // bit per curve: no halved scalars (GLV) for that curve's one-launch MSMs -- set by the prover and by kg_msm_begin around their launches, which are bound by the kernels and not by the host chains GLV halves
   bool inputs_complete = false;          // kg_ctx_set_inputs_complete: MSM inputs are complete when the call is made
 
@@ -61,61 +122,48 @@ struct kg_ctx {
   // hipMalloc allocation runs at 1-5 GB/s (its pages are mapped on first touch: 15-28 ms per 32 MiB, measured), a copy into a block
   // that has been used before at 56 GB/s -- and every host of the boundary allocates per call (DeviceBuf::new in the Rust glue,
   // DeviceBuffer in the C++ mirror, Context.upload in Python)
-  std::multimap<size_t, void*> pool_free;            // size class -> released blocks
-  size_t pool_cached = 0;                            // bytes sitting in pool_free
-  void* ws_vec = nullptr;                // kg_r1cs_prod: work list of long rows (grow-only)
-  size_t ws_vec_bytes = 0;
-  void* ws2 = nullptr;                   // NTT ping-pong buffer
-  size_t ws2_bytes = 0;
-  void* ws3[2] = {nullptr, nullptr};     // prover polynomial buffers (a, b, c, z, transform scratch), one set per proof ticket
-  size_t ws3_bytes[2] = {0, 0};
+  std::multimap<size_t, void*> pool_free;            // size class -> released blocks   } both under capi.cpp's g_pool_mu; the blocks are
+  size_t pool_cached = 0;                            // bytes sitting in pool_free      } released by kg_ctx_destroy's prelude
+  kg::DevBuf ws_vec;                     // kg_r1cs_prod: work list of long rows
+  kg::DevBuf ws2;                        // NTT ping-pong buffer
+  kg::DevBuf ws3[2];                     // prover polynomial buffers (a, b, c, z, transform scratch), one set per proof ticket
   static constexpr int RUN_SETS = 8;     // a slow reduction (G2) may overlap all the later accumulations of a proof
-  void* ws_run[RUN_SETS] = {};           // MSM base-side scratch (packed bases, partial sums, halving buffers), one set per slot mod RUN_SETS
-  size_t ws_run_bytes[RUN_SETS] = {};
-  hipStream_t side_stream = nullptr;     // bucket reduction of MSM i overlaps the accumulation of MSM i+1
-  hipStream_t side2_stream = nullptr;    // second reduction queue (odd slots): a slow G2 reduction does not hold up the next MSM's
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t ev_acc[RUN_SETS] = {};
-  hipEvent_t ev_info[MAX_GROUPS] = {};   // marks the task-count read-back of msm_sort (per window group)
-  struct Slot { void* host = nullptr; void* host_dev = nullptr; size_t bytes = 0; hipEvent_t done = nullptr; int W = 0, c = 0, w0 = 0; bool busy = false;
+  kg::DevBuf ws_run[RUN_SETS];           // MSM base-side scratch (packed bases, partial sums, halving buffers), one set per slot mod RUN_SETS
+  kg::Event ev_fork, ev_join[3];
+  kg::Event ev_acc[RUN_SETS];
+  kg::Event ev_info[MAX_GROUPS];         // marks the task-count read-back of msm_sort (per window group)
+  struct Slot { kg::PinBuf host; kg::Event done; int W = 0, c = 0, w0 = 0; bool busy = false;      // host.mem().dev: the device view the kernels write through
                 bool combined = false; };   // w0: first window of the group the slot holds; combined: ONE point per window (the short-input MSM adds a window's bit planes on the device), otherwise c bit-plane sums per window
   static constexpr int NSLOTS = 24;      // 0 kg_msm, 1..4 kg_msm_begin tickets, 6..10 prover job 0, 11..15 prover job 1, 16..23 slices of kg_msm_host / kg_msm_host_scalars, 16..19 window groups / index slices of kg_msm (blocking calls: never at the same time)
   Slot slots[NSLOTS];
-  void* ws_small[NSLOTS] = {};           // short-input MSM (msm_small.hip): plane points of a window split over several workgroups, per result slot (grow-only)
-  size_t ws_small_bytes[NSLOTS] = {};
-  void* ws_small_batch = nullptr;        // batched short-input MSM (msm_small_batch.hip): window sums and plane points of one launch group (grow-only)
-  size_t ws_small_batch_bytes = 0;
+  kg::DevBuf ws_small[NSLOTS];           // short-input MSM (msm_small.hip): plane points of a window split over several workgroups, per result slot
+  kg::DevBuf ws_small_batch;             // batched short-input MSM (msm_small_batch.hip): window sums and plane points of one launch group
   std::unique_ptr<kg::WorkerPool> workers;   // host worker threads (worker_pool.h), started on demand, alive until the context is destroyed
   std::shared_ptr<void> prover_jobs;     // groth16.hip: proofs in flight (kg_groth16_prove_begin / _end)
-  size_t ticket_n[4] = {0, 0, 0, 0};
+  size_t ticket_n[4] = {0, 0, 0, 0};     // lengths of the MSMs begun with kg_msm_begin
   // kg_msm_begin starts the ticket's host finish (wait for the reduction, 255-step double-and-add, inversion) on a worker
   // thread, so the calling thread goes straight on to enqueue the next MSM; kg_msm_end joins it
   std::future<int> ticket_fut[4];
   uint64_t ticket_out[4][24] = {};
   // table: optional window multiples of the array (kg_bases_precompute): table[w][i] = 2^(table_c * w) * base[i] in resident
   // form, w < table_W -- an MSM against them needs one set of buckets for all windows (merged sort, msm.hip)
-  struct Registered { const uint64_t* base; const uint8_t* inf; size_t n; int curve; uint32_t* packed; uint32_t* table = nullptr; int table_c = 0, table_W = 0; bool fmt64 = false, table64 = false; };   // fmt64 / table64: 64-byte points (msm.hip, BaseIO::load_point64)
-  std::vector<Registered> registered;    // bases converted once by kg_bases_register     // lengths of the MSMs begun with kg_msm_begin                         // pinned result slots: MSMs in flight whose host finish is pending
-  // kg_msm_host: cached device copies of the caller's host arrays (grow-only) and the upload queue
-  void* up_buf[3] = {nullptr, nullptr, nullptr};     // bases, scalars, identity flags
-  size_t up_bytes[3] = {0, 0, 0};
-  hipStream_t up_stream = nullptr;
+  struct Registered { const uint64_t* base; const uint8_t* inf; size_t n; int curve; kg::DevBuf packed, table; int table_c = 0, table_W = 0; bool fmt64 = false, table64 = false; };   // fmt64 / table64: 64-byte points (msm.hip, BaseIO::load_point64)
+  std::vector<Registered> registered;    // bases converted once by kg_bases_register
+  // kg_msm_host: cached device copies of the caller's host arrays
+  kg::DevBuf up_buf[3];                  // bases, scalars, identity flags
   static constexpr int UP_SLICES = 8;    // index slices of a host-array MSM (kg_msm_host, kg_msm_host_scalars): result slots 16 .. 23
-  hipEvent_t ev_up_s[UP_SLICES] = {}, ev_up_b[UP_SLICES] = {};
-  void* ws_points = nullptr;             // kg_points_check (points.hip): the two summary words and the five host points of a CRS check
-  void* fb_tmp = nullptr;                // XYZZ results between the two passes of kg_fixed_base_mul (grow-only)
-  size_t fb_tmp_bytes = 0;
-  uint32_t* fb_table[3] = {nullptr, nullptr, nullptr};   // kg_fixed_base_mul: 32 x 255 generator multiples d * 2^(8w) * G per curve, resident form
-  void* h_pinned = nullptr;              // small pinned staging buffer for results
-  void* h_pinned_dev = nullptr;          // its device view (kernels write the sort's result words straight into it)
-  size_t h_pinned_bytes = 0;
-  std::vector<kg_tw_cache*> tw;          // per-(log_n, inverse) twiddle tables
+  kg::Event ev_up_s[UP_SLICES], ev_up_b[UP_SLICES];
+  kg::DevBuf ws_points;                  // kg_points_check (points.hip): the two summary words and the five host points of a CRS check
+  kg::DevBuf fb_tmp;                     // XYZZ results between the two passes of kg_fixed_base_mul
+  kg::DevBuf fb_table[3];                // kg_fixed_base_mul: 32 x 255 generator multiples d * 2^(8w) * G per curve, resident form
+  kg::PinBuf h_pinned;                   // small pinned staging buffer for results (kernels write the sort's result words straight into its device view)
+  std::vector<kg_tw_cache*> tw;          // per-(log_n, inverse) twiddle tables (ntt.hip's cache: released by tw_cache_free)
   bool tw_fresh = false;                 // tables were built on the main queue since the last fork (transform lanes must wait for them)
   // profiling
   bool prof = false;
   struct Phase { const char* name; hipEvent_t e0, e1; };
   std::vector<Phase> phases;
-  std::vector<hipEvent_t> event_pool;
+  std::vector<kg::Event> event_pool;
   size_t event_next = 0;
   std::atomic<long long> host_finish_us{0};   // summed wall time of the host finishes (double-and-add + inversion) since the last
   std::atomic<int> host_finish_calls{0};      // reset; atomics: a prover's finishes run on up to five worker threads at once
@@ -164,18 +212,36 @@ struct JoinGuard {
 // repeated once (the pool must never be what makes a call fail)
 hipError_t dev_alloc(kg_ctx* c, void** p, size_t bytes);
 void pool_trim(kg_ctx* c);               // releases every kept block
-int ensure_ws_sort(kg_ctx* c, int set, size_t bytes);
 int make_sort_stream(kg_ctx* c);
 hipError_t create_stream(kg_ctx* c, hipStream_t* out, bool service);
-int ensure_ws2(kg_ctx* c, size_t bytes);
-int ensure_ws_vec(kg_ctx* c, size_t bytes);
-int ensure_ws3(kg_ctx* c, int which, size_t bytes);
-int ensure_ws_run(kg_ctx* c, int which, size_t bytes);
-int ensure_slot(kg_ctx* c, int slot, size_t bytes);
-int ensure_pinned(kg_ctx* c, size_t bytes);
+int ensure_slot(kg_ctx* c, int slot, size_t bytes);      // the slot's event and its pinned buffer
 int make_side_stream(kg_ctx* c);
 int slice_table_window(const kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t cnt);
 void sync_all(kg_ctx* c);
+inline int DevMem::alloc(void** p, size_t bytes) {
+  const hipError_t e = dev_alloc(c, p, bytes);
+  return e == hipSuccess ? KG_OK : set_err(c, KG_ERR_OOM, what, e);
+}
+inline void DevMem::drain_before_release() { sync_all(c); }
+inline int PinMem::alloc(void** p, size_t bytes) {
+  dev = nullptr;
+  hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+  if (e != hipSuccess) return set_err(c, KG_ERR_OOM, (std::string(what) + " allocation").c_str(), e);
+  if ((e = hipHostGetDevicePointer(&dev, *p, 0)) == hipSuccess) return KG_OK;
+  (void)hipHostFree(*p);
+  return set_err(c, KG_ERR_HIP, (std::string(what) + " device view").c_str(), e);
+}
+// Does the registered array r hold [d_bases, d_bases + n) of this curve with these identity flags?  *off: index of the first point in r.
+// (The flags were baked in at registration: the resident copy serves a call only when the call's flag array is the registered one at
+// the same offset, or both are absent; any other combination converts per call.)
+inline bool covers(const kg_ctx::Registered& r, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t n, size_t* off) {
+  const size_t pw64 = curve == KG_G2 ? 16 : 8;             // u64 words per ABI point
+  if (r.curve != curve || d_bases < r.base) return false;
+  const size_t off64 = (size_t)(d_bases - r.base);
+  if (off64 % pw64 != 0 || off64 / pw64 + n > r.n) return false;
+  *off = off64 / pw64;
+  return d_inf == (r.inf ? r.inf + *off : nullptr);
+}
 
 // RAII-free phase timer: PhaseScope p(ctx, "name"); ... p.end();
 struct PhaseScope {
@@ -221,7 +287,7 @@ inline Words8 words8(const uint64_t h[4]) {
 struct RowWs {
   static constexpr int REGIONS = 3;
   static constexpr size_t words(size_t m) { return m + 16; }                       // of one region for m rows
-  static constexpr size_t bytes(size_t m) { return REGIONS * words(m) * 4; }       // what ensure_ws_vec is asked for
+  static constexpr size_t bytes(size_t m) { return REGIONS * words(m) * 4; }       // what kg_ctx::ws_vec is asked for
   uint32_t* count;      // [0]: rows on the list's front (a wave each), [1]: rows on its back (kg_r1cs_prod's huge rows, a workgroup each)
   uint32_t* summary;    // kg_r1cs_check: bad rows | first bad row (BadSummary)
   uint32_t* list;       // the work list of long rows: up to m entries

@@ -260,37 +260,29 @@ int fixed_base_t(kg_ctx* ctx, int curve, const uint64_t* d_k, size_t n, uint64_t
       for (int d = 1; d <= FB_ENT; ++d) hk[((size_t)w * FB_ENT + (d - 1)) * 4 + (size_t)(w / 8)] = (uint64_t)d << (8 * (w % 8));
     // (w = 31: d * 2^248 may exceed the group order; it is used as a plain integer multiple, which is what the table needs --
     // the double-and-add below takes the canonical 254 bits of k mod p only, so reduce on the host instead)
-    uint64_t *d_tk = nullptr, *d_txy = nullptr; uint8_t* d_tinf = nullptr; uint32_t* table = nullptr;
-    auto release = [&](bool keep_table) {             // every exit below frees what was allocated before it
-      hipFree(d_tk); hipFree(d_txy); hipFree(d_tinf);
-      if (!keep_table) hipFree(table);
-    };
-    hipError_t e = dev_alloc(ctx, (void**)&d_tk, tn * 32);
-    if (e == hipSuccess) e = dev_alloc(ctx, (void**)&d_txy, tn * 2 * E64 * 8);
-    if (e == hipSuccess) e = dev_alloc(ctx, (void**)&d_tinf, tn);
-    if (e == hipSuccess) e = dev_alloc(ctx, (void**)&table, tn * PW * 4);
-    if (e != hipSuccess) { release(false); return set_err(ctx, KG_ERR_OOM, "fixed-base table allocation", e); }
-    e = hipMemcpyAsync(d_tk, hk.data(), tn * 32, hipMemcpyHostToDevice, st);
+    DevBuf b_tk, b_txy, b_tinf, b_table;              // every exit below releases what was allocated before it
+    const DevMem mem{ctx, "fixed-base table allocation"};
+    KG_TRY(b_tk.ensure(mem, tn * 32));
+    KG_TRY(b_txy.ensure(mem, tn * 2 * E64 * 8));
+    KG_TRY(b_tinf.ensure(mem, tn));
+    KG_TRY(b_table.ensure(mem, tn * PW * 4));
+    uint64_t *d_tk = b_tk.as<uint64_t>(), *d_txy = b_txy.as<uint64_t>(); uint8_t* d_tinf = b_tinf.as<uint8_t>(); uint32_t* table = b_table.as<uint32_t>();
+    hipError_t e = hipMemcpyAsync(d_tk, hk.data(), tn * 32, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { release(false); return set_err(ctx, KG_ERR_HIP, "fixed-base table upload", e); }
+    if (e != hipSuccess) return set_err(ctx, KG_ERR_HIP, "fixed-base table upload", e);
     int rc = kg_field_vec_op(ctx, curve == KG_GRUMPKIN ? KG_FQ : KG_FR, KG_OP_TO_MONT, d_tk, nullptr, d_tk, tn);
     if (rc == KG_OK) {
       hipLaunchKernelGGL((k_fixed_base_mul<F, SP, E64>), dim3((unsigned)((tn + 63) / 64)), dim3(64), 0, st, d_tk, tn, d_txy, d_tinf);
       hipLaunchKernelGGL((k_fb_pack<F, E64>), dim3((unsigned)((tn + 63) / 64)), dim3(64), 0, st, d_txy, tn, table);
       if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = set_err(ctx, KG_ERR_HIP, "fixed-base table construction");
     }
-    release(rc == KG_OK);
     if (rc != KG_OK) return rc;
-    ctx->fb_table[curve] = table;
+    ctx->fb_table[curve] = std::move(b_table);
   }
   constexpr int NW = PointIO<F>::NW;
-  if (n * NW * 4 > ctx->fb_tmp_bytes) {
-    if (ctx->fb_tmp) { sync_all(ctx); hipFree(ctx->fb_tmp); ctx->fb_tmp = nullptr; ctx->fb_tmp_bytes = 0; }
-    KG_HIP(ctx, dev_alloc(ctx, &ctx->fb_tmp, n * NW * 4));
-    ctx->fb_tmp_bytes = n * NW * 4;
-  }
-  uint32_t* tmp = (uint32_t*)ctx->fb_tmp;
-  hipLaunchKernelGGL((k_fb_window<F, SP>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, d_k, n, ctx->fb_table[curve], tmp);
+  KG_TRY(ctx->fb_tmp.ensure(DevMem{ctx, "fixed-base scratch allocation"}, n * NW * 4));
+  uint32_t* tmp = ctx->fb_tmp.as<uint32_t>();
+  hipLaunchKernelGGL((k_fb_window<F, SP>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, d_k, n, ctx->fb_table[curve].as<const uint32_t>(), tmp);
   const size_t lanes = (n + FB_BATCH - 1) / FB_BATCH;
   hipLaunchKernelGGL((k_fb_affine<F, E64>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st, tmp, n, d_out_xy, d_out_inf);
   KG_HIP(ctx, hipGetLastError());
@@ -397,8 +389,8 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
   // polynomial buffers of this ticket: a, b, c (n each), z = x || w, three transform scratch vectors.  One set per ticket,
   // so the next proof's transforms and witness sort start while this proof is still accumulating.
   const int tk = slot_base >= 10 ? 1 : 0;
-  KG_TRY(ensure_ws3(ctx, tk, (6 * n + l + m_l_1) * 32));
-  uint64_t* A = (uint64_t*)ctx->ws3[tk];
+  KG_TRY(ctx->ws3[tk].ensure(DevMem{ctx, "prover buffer allocation"}, (6 * n + l + m_l_1) * 32));
+  uint64_t* A = ctx->ws3[tk].as<uint64_t>();
   uint64_t* B = A + 4 * n;
   uint64_t* C = B + 4 * n;
   uint64_t* Z = C + 4 * n;                                // z = x || w
@@ -413,10 +405,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
   // blocking; with reductions that fit beside an accumulation it wins -- EXPERIMENTS.md Part I section 11.  KG_G16_H_EARLY = 0 is the old
   // order, = 2 puts h's chain in front of the G2 accumulation.)
   if (!ctx->side_stream) KG_TRY(make_side_stream(ctx));
-  if (!ctx->ev_fork) {
-    KG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    for (int i = 0; i < 3; ++i) KG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming));
-  }
+  KG_HIP(ctx, create_events({ctx->ev_fork, ctx->ev_join}));
   if (do_h) {
     KG_TRY(ntt_prepare(ctx, k, 0));
     KG_TRY(ntt_prepare(ctx, k, 1));
@@ -441,7 +430,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
   if (need_z && m_l_1) KG_HIP(ctx, hipMemcpyAsync(Z + 4 * l, d_w, m_l_1 * 32, hipMemcpyDeviceToDevice, sq));
   if (mats && do_h) {
     if (m >= ((size_t)1 << 32)) return set_err(ctx, KG_ERR_BAD_ARG, "more than 2^32 constraints");
-    KG_TRY(ensure_ws_vec(ctx, RowWs::bytes(m)));
+    KG_TRY(ctx->ws_vec.ensure(DevMem{ctx, "workspace allocation"}, RowWs::bytes(m)));
     KG_HIP(ctx, hipEventRecord(ctx->ev_order, sq));       // z is complete: the matrix-vector products of the chains wait for it
   }
   MsmSorted Sz;
@@ -508,7 +497,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
     if (mats) {                                           // row v of cs.evaluate(): M_v z, z as the scalar queue assembled it
       hip_rc(hipStreamWaitEvent(sv, ctx->ev_order, 0), "hipStreamWaitEvent(z)");
       if (rc == KG_OK) rc = r1cs_prod_enqueue(ctx, sv, KG_FR, mats[v]->d_row_ptr, mats[v]->d_col, mats[v]->d_val, m, Z, dst[v],
-                                              RowWs(ctx->ws_vec, m, v));
+                                              RowWs(ctx->ws_vec.get(), m, v));
     } else
       hip_rc(hipMemcpyAsync(dst[v], src[v], m * 32, hipMemcpyDeviceToDevice, sv), "hipMemcpyAsync(evaluations)");
     if (n > m) hip_rc(hipMemsetAsync(dst[v] + 4 * m, 0, (n - m) * 32, sv), "hipMemsetAsync(padding)");
@@ -533,7 +522,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
   // fork event like every other part of the proof, the caller's queue carries nothing of ours and proof i + 1 starts beside proof i.
   hipStream_t hq = st;
   if (small && fork && !alone_front && do_h) {
-    if (!ctx->acc_stream[0]) hip_rc(create_stream(ctx, &ctx->acc_stream[0], false), "queue creation");
+    if (!ctx->acc_stream[0]) hip_rc(create_stream(ctx, &ctx->acc_stream[0].h, false), "queue creation");
     if (ctx->acc_stream[0]) { hq = ctx->acc_stream[0]; hip_rc(hipStreamWaitEvent(hq, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)"); }
   }
   auto h_front = [&]() {                                  // h = (a o b - c) / Z on the coset, back to coefficients (prover.rs:43-47)
@@ -581,7 +570,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
       for (int k = 0; k < 3 && rc == KG_OK; ++k) {
         if (q3[k].n == 0) { msm_identity(KG_G1, q3[k].out); continue; }
         hipStream_t qk = ctx->acc_stream[1 + k];
-        if (!qk) { hip_rc(create_stream(ctx, &ctx->acc_stream[1 + k], false), "queue creation"); qk = ctx->acc_stream[1 + k]; }
+        if (!qk) { hip_rc(create_stream(ctx, &ctx->acc_stream[1 + k].h, false), "queue creation"); qk = ctx->acc_stream[1 + k]; }
         if (rc != KG_OK) break;
         hip_rc(hipStreamWaitEvent(qk, ctx->ev_order, 0), "hipStreamWaitEvent(z)");
         if (rc == KG_OK) rc = msm_small_enqueue(ctx, qk, KG_G1, q3[k].b, q3[k].inf, q3[k].sc, q3[k].n, q3[k].slot, q3[k].c, q3[k].r);

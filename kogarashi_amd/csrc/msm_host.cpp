@@ -78,7 +78,7 @@ int msm_finish_t(kg_ctx* ctx, const int* slots, int nslots, uint64_t* out_xyz) {
     if (hipEventSynchronize(sl.done) != hipSuccess) return KG_ERR_HIP;
     host_trace("finish: slot ready");
     const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t* hp = (const uint64_t*)sl.host;
+    const uint64_t* hp = sl.host.as<const uint64_t>();
     const int W = sl.W, c = sl.c, w0 = sl.w0;
     if (sl.combined) {                                     // one point per window (msm_small.hip): 2^c * acc + S_w
       for (int w = W - 1; w >= 0; --w) {
@@ -213,7 +213,7 @@ static int msm_grouped(kg_ctx* ctx, int curve, const uint64_t* d_bases, const ui
   if (!ctx->side_stream) KG_TRY(make_side_stream(ctx));
   KG_TRY(make_sort_stream(ctx));
   for (int g = 1; g < NG && g < ctx->tune.group_accq; ++g)      // only the queues the groups rotate over (two: acc_stream[1] comes placed from place_queues)
-    if (!ctx->acc_stream[g]) KG_HIP(ctx, create_stream(ctx, &ctx->acc_stream[g], false));
+    if (!ctx->acc_stream[g]) KG_HIP(ctx, create_stream(ctx, &ctx->acc_stream[g].h, false));
   kg::MsmSortPlan Q;
   // KG_GROUP_MAIN_FIRST=1 (experiment): conversion and the first group's sort on the main queue, in front of its accumulation -- no
   // cross-queue hand-over there, but the second group's sort then runs BESIDE the first one's, the two accumulations start 50 us
@@ -227,32 +227,21 @@ static int msm_grouped(kg_ctx* ctx, int curve, const uint64_t* d_bases, const ui
   }
   // the bases: a registered array is resident already; otherwise ONE conversion for all groups, on a reduction queue (idle
   // at this point) beside the scalar conversion
-  const size_t pw64 = curve == KG_G2 ? 16 : 8;             // u64 words per ABI point
   bool resident = false;
-  for (const auto& r : ctx->registered) {
-    if (r.curve != curve || d_bases < r.base) continue;
-    const size_t off64 = (size_t)(d_bases - r.base);
-    if (off64 % pw64 != 0 || off64 / pw64 + n > r.n) continue;
-    if (d_inf != (r.inf ? r.inf + off64 / pw64 : nullptr)) continue;
-    resident = true;
-    break;
-  }
+  size_t off = 0;
+  for (const auto& r : ctx->registered)
+    if (covers(r, curve, d_bases, d_inf, n, &off)) { resident = true; break; }
   const bool f64 = resident_fmt64(n);
   if (!resident) {
     const size_t bytes = n * (f64 ? (curve == KG_G2 ? 128 : 64) : (curve == KG_G2 ? 144 : 72));
-    if (bytes > ctx->ws_pb_bytes) {
-      if (ctx->ws_pb) { sync_all(ctx); hipFree(ctx->ws_pb); ctx->ws_pb = nullptr; ctx->ws_pb_bytes = 0; }
-      const hipError_t e = dev_alloc(ctx, &ctx->ws_pb, bytes + bytes / 8);
-      if (e != hipSuccess) return set_err(ctx, KG_ERR_OOM, "resident-bases allocation", e);
-      ctx->ws_pb_bytes = bytes + bytes / 8;
-    }
+    KG_TRY(ctx->ws_pb.ensure(DevMem{ctx, "resident-bases allocation"}, bytes, bytes / 8));
     hipStream_t cq = ctx->side_stream;
     if (!ctx->inputs_complete) {                          // stream semantics: the bases may still be in flight on the main queue
       KG_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
       KG_HIP(ctx, hipStreamWaitEvent(cq, ctx->ev_order, 0));
     }
     PhaseScope ph(ctx, "prep_bases", cq);
-    prep_bases_enqueue(curve, cq, d_bases, d_inf, n, (uint32_t*)ctx->ws_pb, f64);
+    prep_bases_enqueue(curve, cq, d_bases, d_inf, n, ctx->ws_pb.as<uint32_t>(), f64);
     ph.end();
     KG_HIP(ctx, hipGetLastError());
     KG_HIP(ctx, hipEventRecord(ctx->ev_pb, cq));
@@ -280,7 +269,7 @@ static int msm_grouped(kg_ctx* ctx, int curve, const uint64_t* d_bases, const ui
     S[g].tail_alone = g == NG - 1;                          // the last group's tail has the chip
     const int one_side = ctx->tune.group_one_side;
     slots[g] = one_side ? 16 + 2 * g : 16 + g;
-    kg::MsmRunJob job{d_bases, d_inf, n, 0u, slots[g], false, resident ? nullptr : (const uint32_t*)ctx->ws_pb, f64};
+    kg::MsmRunJob job{d_bases, d_inf, n, 0u, slots[g], false, resident ? nullptr : ctx->ws_pb.as<const uint32_t>(), f64};
     rc = kg::msm_run_multi(ctx, S[g], curve, &job, 1);
     if (rc != KG_OK) break;
     ++launched;
@@ -344,16 +333,12 @@ int kg_bases_register(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uin
   kg_bases_unregister(ctx, d_bases);
   const bool fmt64 = resident_fmt64(n);
   const size_t pw = fmt64 ? (curve == KG_G2 ? 32 : 16) : (curve == KG_G2 ? 36 : 18);
-  uint32_t* packed = nullptr;
-  KG_HIP(ctx, dev_alloc(ctx, (void**)&packed, n * pw * 4));
-  prep_bases_enqueue(curve, ctx->stream, d_bases, d_inf, n, packed, fmt64);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) {
-    hipFree(packed);
-    return set_err(ctx, KG_ERR_HIP, "k_prep_bases launch", e);
-  }
-  kg_ctx::Registered reg{d_bases, d_inf, n, curve, packed};
+  kg_ctx::Registered reg{d_bases, d_inf, n, curve};
   reg.fmt64 = fmt64;
-  ctx->registered.push_back(reg);
+  KG_TRY(reg.packed.ensure(DevMem{ctx, "registered-bases allocation"}, n * pw * 4));
+  prep_bases_enqueue(curve, ctx->stream, d_bases, d_inf, n, reg.packed.as<uint32_t>(), fmt64);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return set_err(ctx, KG_ERR_HIP, "k_prep_bases launch", e);
+  ctx->registered.push_back(std::move(reg));
   return KG_OK;
   });
 }
@@ -363,10 +348,7 @@ int kg_bases_unregister(kg_ctx* ctx, const uint64_t* d_bases) {
   if (!ctx) return KG_ERR_BAD_ARG;
   for (size_t i = 0; i < ctx->registered.size(); ++i) {
     if (ctx->registered[i].base == d_bases) {
-      kg_ctx_sync(ctx);
-      hipFree(ctx->registered[i].packed);
-      if (ctx->registered[i].table) hipFree(ctx->registered[i].table);
-      ctx->registered.erase(ctx->registered.begin() + i);
+      ctx->registered.erase(ctx->registered.begin() + i);      // drains the context's queues and releases both resident forms
       return KG_OK;
     }
   }
@@ -386,15 +368,13 @@ int kg_bases_precompute(kg_ctx* ctx, const uint64_t* d_bases, size_t msm_len) {
   const int c = kg::merged_window(ctx, msm_len);
   if (!c) return set_err(ctx, KG_ERR_BAD_ARG, "kg_bases_precompute: window tables are offered for MSMs of 2^16 .. 2^20 scalars");
   if (r->table && r->table_c == c) return KG_OK;
-  if (r->table) { kg_ctx_sync(ctx); hipFree(r->table); r->table = nullptr; r->table_c = r->table_W = 0; }
+  r->table.reset();                                        // a table of another width goes first (drained): its memory is the new one's headroom
+  r->table_c = r->table_W = 0;
   const int W = (255 + c - 1) / c;
   const bool t64 = table_fmt64();
   const size_t pw = t64 ? (r->curve == KG_G2 ? 32 : 16) : (r->curve == KG_G2 ? 36 : 18), row = r->n * pw;
-  uint32_t* table = nullptr;
-  if (hipError_t e = dev_alloc(ctx, (void**)&table, (size_t)W * row * 4); e != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(ctx, KG_ERR_OOM, "window table allocation", e);
-  }
+  KG_TRY(r->table.ensure(DevMem{ctx, "window table allocation"}, (size_t)W * row * 4));
+  uint32_t* const table = r->table.as<uint32_t>();
   hipStream_t st = ctx->stream;
   // row 0 from the caller's array (the resident copy may be in the other form), then one launch per further window
   prep_bases_enqueue(r->curve, st, r->base, r->inf, r->n, table, t64);
@@ -403,8 +383,8 @@ int kg_bases_precompute(kg_ctx* ctx, const uint64_t* d_bases, size_t msm_len) {
     table_next_enqueue(r->curve, st, table + (size_t)(w - 1) * row, r->n, c, table + (size_t)w * row, t64);
     e = hipGetLastError();
   }
-  if (e != hipSuccess) { hipFree(table); return set_err(ctx, KG_ERR_HIP, "window table build", e); }
-  r->table = table; r->table_c = c; r->table_W = W; r->table64 = t64;
+  if (e != hipSuccess) { r->table.reset(); return set_err(ctx, KG_ERR_HIP, "window table build", e); }
+  r->table_c = c; r->table_W = W; r->table64 = t64;
   return KG_OK;
   });
 }
@@ -469,15 +449,6 @@ int kg_msm_end(kg_ctx* ctx, int curve, int ticket, uint64_t* out_xyz) {
 //                        the bases of groth16/src/msm.rs:6 / nova/src/pedersen.rs:15-20 are fixed, the scalars are new.
 // Only the FIRST slice's upload is exposed (everything downstream needs its scalars), so it is the short one:
 // msm_host_plan cuts the range into one half-share and K - 1 full shares.
-static int grow_device(kg_ctx* ctx, int which, size_t bytes) {
-  if (bytes <= ctx->up_bytes[which]) return KG_OK;
-  if (ctx->up_buf[which]) { sync_all(ctx); hipFree(ctx->up_buf[which]); ctx->up_buf[which] = nullptr; ctx->up_bytes[which] = 0; }
-  const hipError_t e = dev_alloc(ctx, &ctx->up_buf[which], bytes + bytes / 8);
-  if (e != hipSuccess) { (void)hipGetLastError(); return set_err(ctx, KG_ERR_OOM, "upload buffer allocation", e); }
-  ctx->up_bytes[which] = bytes + bytes / 8;
-  return KG_OK;
-}
-
 // Slice boundaries lo[0 .. K] of an n-pair host-array MSM; returns K.  scalars_only: the bases are resident.
 //   both arrays : 4 equal slices from 2^20 pairs, 2 from 2^18 (the bus is the floor).  Measured, K = 1 / 2 / 4 (round 5, ms): 2^16 0.67 / 0.84 / 1.16,
 //                 2^17 0.93 / 1.01 / 1.24, 2^18 1.28 / 1.22 / 1.54, 2^19 1.99 / 1.78 / 1.86, 2^20 3.62 / 2.95 / 2.80
@@ -518,18 +489,16 @@ static int msm_host_impl(kg_ctx* ctx, int curve, const uint64_t* bases, const ui
   KG_HIP(ctx, hipSetDevice(ctx->device));
   host_trace("host: enter");
   const size_t pb = curve == KG_G2 ? 128 : 64;             // bytes per base
+  const DevMem up_mem{ctx, "upload buffer allocation"};
   if (!bases_on_device) {
-    KG_TRY(grow_device(ctx, 0, n * pb));
-    if (inf) KG_TRY(grow_device(ctx, 2, n));
+    KG_TRY(ctx->up_buf[0].ensure(up_mem, n * pb, n * pb / 8));
+    if (inf) KG_TRY(ctx->up_buf[2].ensure(up_mem, n, n / 8));
   }
-  KG_TRY(grow_device(ctx, 1, n * 32));
-  if (!ctx->ev_up_s[0]) {
+  KG_TRY(ctx->up_buf[1].ensure(up_mem, n * 32, n * 32 / 8));
+  if (!ctx->ev_up_b[kg_ctx::UP_SLICES - 1]) {              // (the last one created: a failure half-way is made up for by the next call)
     KG_TRY(make_sort_stream(ctx));                         // places the context's queues, the upload queue among them
-    if (!ctx->up_stream) KG_HIP(ctx, hipStreamCreateWithFlags(&ctx->up_stream, hipStreamNonBlocking));
-    for (int i = 0; i < kg_ctx::UP_SLICES; ++i) {
-      KG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_up_s[i], hipEventDisableTiming));
-      KG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_up_b[i], hipEventDisableTiming));
-    }
+    if (!ctx->up_stream) KG_HIP(ctx, hipStreamCreateWithFlags(&ctx->up_stream.h, hipStreamNonBlocking));
+    KG_HIP(ctx, create_events({ctx->ev_up_s, ctx->ev_up_b}));
   }
   hipStream_t sq;
   KG_TRY(kg::scalar_queue(ctx, &sq));
@@ -537,16 +506,16 @@ static int msm_host_impl(kg_ctx* ctx, int curve, const uint64_t* bases, const ui
     KG_HIP(ctx, hipEventRecord(ctx->ev_order, ctx->stream));
     KG_HIP(ctx, hipStreamWaitEvent(sq, ctx->ev_order, 0));
   }
-  const char* d_b = bases_on_device ? (const char*)bases : (const char*)ctx->up_buf[0];
-  uint64_t* d_s = (uint64_t*)ctx->up_buf[1];
-  const uint8_t* d_i = bases_on_device ? inf : (inf ? (const uint8_t*)ctx->up_buf[2] : nullptr);
+  const char* d_b = bases_on_device ? (const char*)bases : ctx->up_buf[0].as<const char>();
+  uint64_t* d_s = ctx->up_buf[1].as<uint64_t>();
+  const uint8_t* d_i = bases_on_device ? inf : (inf ? ctx->up_buf[2].as<const uint8_t>() : nullptr);
   int sc = 0, sr = 0;
   if (kg::msm_small_plan(ctx, curve, n, &sc, &sr)) {
     // short inputs: the arrays go up on the main queue (a few KB: the copies are staged and return at once), the one-launch MSM behind them
     KG_HIP(ctx, hipMemcpyAsync(d_s, h_scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
     if (!bases_on_device) {
-      KG_HIP(ctx, hipMemcpyAsync(ctx->up_buf[0], bases, n * pb, hipMemcpyHostToDevice, ctx->stream));
-      if (inf) KG_HIP(ctx, hipMemcpyAsync(ctx->up_buf[2], inf, n, hipMemcpyHostToDevice, ctx->stream));
+      KG_HIP(ctx, hipMemcpyAsync(ctx->up_buf[0].get(), bases, n * pb, hipMemcpyHostToDevice, ctx->stream));
+      if (inf) KG_HIP(ctx, hipMemcpyAsync(ctx->up_buf[2].get(), inf, n, hipMemcpyHostToDevice, ctx->stream));
     }
     KG_TRY(kg::msm_small_enqueue(ctx, ctx->stream, curve, (const uint64_t*)d_b, d_i, d_s, n, 0, sc, sr));
     return kg::msm_finish(ctx, curve, 0, out_xyz);
@@ -569,8 +538,8 @@ static int msm_host_impl(kg_ctx* ctx, int curve, const uint64_t* bases, const ui
   auto upload_bases = [&](int j) {
     if (!bases_on_device) {
       const size_t a = lo[j], cnt = lo[j + 1] - lo[j];
-      hipError_t e = hipMemcpyAsync((char*)ctx->up_buf[0] + a * pb, (const char*)bases + a * pb, cnt * pb, hipMemcpyHostToDevice, ctx->up_stream);
-      if (e == hipSuccess && inf) e = hipMemcpyAsync((uint8_t*)ctx->up_buf[2] + a, inf + a, cnt, hipMemcpyHostToDevice, ctx->up_stream);
+      hipError_t e = hipMemcpyAsync(ctx->up_buf[0].as<char>() + a * pb, (const char*)bases + a * pb, cnt * pb, hipMemcpyHostToDevice, ctx->up_stream);
+      if (e == hipSuccess && inf) e = hipMemcpyAsync(ctx->up_buf[2].as<uint8_t>() + a, inf + a, cnt, hipMemcpyHostToDevice, ctx->up_stream);
       if (e == hipSuccess) e = hipEventRecord(ctx->ev_up_b[j], ctx->up_stream);
       if (e != hipSuccess) up_rc = (int)e;
       host_trace("upload: bases");
@@ -591,7 +560,7 @@ static int msm_host_impl(kg_ctx* ctx, int curve, const uint64_t* bases, const ui
     return msm_blocking(ctx, curve, bases, inf, d_s, n, out_xyz);
   }
   // (everything that can fail and return comes before the uploader thread exists)
-  if (K > 1 && !ctx->acc_stream[1]) { if (create_stream(ctx, &ctx->acc_stream[1], false) != hipSuccess) return set_err(ctx, KG_ERR_HIP, "queue creation"); }
+  if (K > 1 && !ctx->acc_stream[1]) { if (create_stream(ctx, &ctx->acc_stream[1].h, false) != hipSuccess) return set_err(ctx, KG_ERR_HIP, "queue creation"); }
   std::future<int> uploader = kg::pool(ctx).submit([&]() -> int {
     hipSetDevice(ctx->device);
     upload_bases(0);

@@ -27,10 +27,8 @@ namespace kg {
 // Base-side half: accumulate + reduce against up to MAX_FUSED base arrays that share the scalar sort S, export, and start
 // the copy of each result into its host slot.  One accumulation launch serves all arrays (see k_acc_tasks); everything
 // after it runs per array, its reduction on one of the two side queues.
-struct RunJob { const uint64_t* d_bases; const uint8_t* d_inf; size_t nbases; uint32_t idx_off; int slot; bool bases_complete; const uint32_t* packed; bool packed64; };
-
 template <class Cfg>
-int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const RunJob* jobs, int njobs) {
+int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const MsmRunJob* jobs, int njobs) {
   using F = typename Cfg::F;
   using KF = typename Cfg::KF;                      // field type of the reduction kernels (Fq2: a lane pair per task, fp2s.h)
   constexpr unsigned LPT = Lanes<KF>::N;            // lanes per task
@@ -54,7 +52,7 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const RunJob* jobs, int njo
   A.nsets = njobs;
   for (int k = 0; k < MAX_FUSED; ++k) { A.pb[k] = nullptr; A.idx_off[k] = 0; A.partial[k] = nullptr; A.tab_n[k] = 0; A.fmt64[k] = 0; }
   for (int k = 0; k < njobs; ++k) {
-    const RunJob& J = jobs[k];
+    const MsmRunJob& J = jobs[k];
     Lay& Y = lay[k];
     Carver cv;
     const uint32_t* reg_pb = nullptr;               // bases inside a registered array are already in packed internal form
@@ -64,21 +62,16 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const RunJob* jobs, int njo
     }
     for (const auto& r : ctx->registered) {
       if (reg_pb) break;
-      if (r.curve != Cfg::ID || J.d_bases < r.base) continue;
-      const size_t off64 = (size_t)(J.d_bases - r.base);
-      if (off64 % (size_t)BaseIO<F>::W != 0 || off64 / BaseIO<F>::W + J.nbases > r.n) continue;
-      // the identity flags were baked in at registration: the resident copy serves the call only when the call's flag
-      // array is the registered one (same offset), or both are absent; any other combination converts per call
-      const size_t off = off64 / BaseIO<F>::W;
-      if (J.d_inf != (r.inf ? r.inf + off : nullptr)) continue;
+      size_t off = 0;
+      if (!covers(r, Cfg::ID, J.d_bases, J.d_inf, J.nbases, &off)) continue;
       if (S.merged_shift) {                         // merged sort: the whole array through its window table
         // (an index slice of the array reads the same rows from its offset: row w of point i is table[w * r.n + i])
         if (!r.table || r.table_c != c || r.table_W != S.windows) continue;
-        reg_pb = r.table + off * (r.table64 ? 2 * BaseIO<F>::PK : PW);
+        reg_pb = r.table.as<uint32_t>() + off * (r.table64 ? 2 * BaseIO<F>::PK : PW);
         A.tab_n[k] = (uint32_t)r.n;
         A.fmt64[k] = r.table64 ? 1 : 0;
       } else {
-        reg_pb = r.packed + off * (r.fmt64 ? 2 * BaseIO<F>::PK : PW);
+        reg_pb = r.packed.as<uint32_t>() + off * (r.fmt64 ? 2 * BaseIO<F>::PK : PW);
         A.fmt64[k] = r.fmt64 ? 1 : 0;
       }
       break;
@@ -96,10 +89,10 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const RunJob* jobs, int njo
     Y.set = J.slot % kg_ctx::RUN_SETS;              // run space per set: the reductions of the previous MSMs may still read the other sets
     for (int k2 = 0; k2 < k; ++k2)
       if (lay[k2].set == Y.set) return set_err(ctx, KG_ERR_BAD_ARG, "fused MSMs need result slots in different run-space sets");
-    KG_TRY(ensure_ws_run(ctx, Y.set, cv.off));
+    KG_TRY(ctx->ws_run[Y.set].ensure(DevMem{ctx, "msm run-space allocation"}, cv.off, cv.off / 8));
     KG_TRY(ensure_slot(ctx, J.slot, exp_bytes));
-    if (!ctx->ev_acc[Y.set]) KG_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_acc[Y.set], hipEventDisableTiming));
-    Y.ws = (char*)ctx->ws_run[Y.set];
+    KG_HIP(ctx, create_events({ctx->ev_acc[Y.set]}));
+    Y.ws = (char*)ctx->ws_run[Y.set].get();
     Y.pb = reg_pb ? reg_pb : (uint32_t*)(Y.ws + Y.o_pb);
     // this buffer set was last used by an earlier slot: its side-stream work must be over before we overwrite it
     for (int s2 = 0; s2 < kg_ctx::NSLOTS; ++s2)
@@ -145,7 +138,7 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const RunJob* jobs, int njo
     ph.end();
   }
   for (int k = 0; k < njobs; ++k) {
-    const RunJob& J = jobs[k];
+    const MsmRunJob& J = jobs[k];
     const Lay& Y = lay[k];
     const int slot = J.slot, set = Y.set;
     char* ws = Y.ws;
@@ -247,16 +240,16 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const RunJob* jobs, int njo
         static std::atomic<uint64_t> attr_devs{0};      // once per device
         const uint64_t bit = (uint64_t)1 << (ctx->device & 63);
         if (!(attr_devs.load() & bit)) { KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_reduce_tail_coop<F, Cfg::E64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_devs |= bit; }
-        hipLaunchKernelGGL((k_reduce_tail_coop<F, Cfg::E64>), dim3((unsigned)(W * narr)), dim3(TailCoopNT<F>::NT), lds, side, pbuf[cur], in_stride, narr, len, c, (uint64_t*)sl.host_dev);
+        hipLaunchKernelGGL((k_reduce_tail_coop<F, Cfg::E64>), dim3((unsigned)(W * narr)), dim3(TailCoopNT<F>::NT), lds, side, pbuf[cur], in_stride, narr, len, c, (uint64_t*)sl.host.mem().dev);
       } else
       if (len == TL) {
         KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_reduce_tail<KF, Cfg::E64, (int)TL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tail_lds));
-        hipLaunchKernelGGL((k_reduce_tail<KF, Cfg::E64, (int)TL>), dim3((unsigned)(W * narr)), dim3(tail_threads), tail_lds, side, pbuf[cur], in_stride, narr, len, c, (uint64_t*)sl.host_dev);
+        hipLaunchKernelGGL((k_reduce_tail<KF, Cfg::E64, (int)TL>), dim3((unsigned)(W * narr)), dim3(tail_threads), tail_lds, side, pbuf[cur], in_stride, narr, len, c, (uint64_t*)sl.host.mem().dev);
       } else {                                           // a small window (len <= TL / 2): the images keep the stride of the longest such array
         if (len > TL / 2) return set_err(ctx, KG_ERR_UNSUPPORTED, "reduction tail: array length");     // (B is a power of two: never)
         const size_t lds0 = tail_lds_bytes(TL / 2, (int)LPT);
         KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_reduce_tail<KF, Cfg::E64, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0));
-        hipLaunchKernelGGL((k_reduce_tail<KF, Cfg::E64, 0>), dim3((unsigned)(W * narr)), dim3(tail_threads), lds0, side, pbuf[cur], in_stride, narr, len, c, (uint64_t*)sl.host_dev);
+        hipLaunchKernelGGL((k_reduce_tail<KF, Cfg::E64, 0>), dim3((unsigned)(W * narr)), dim3(tail_threads), lds0, side, pbuf[cur], in_stride, narr, len, c, (uint64_t*)sl.host.mem().dev);
       }
       ph.end();
     }
@@ -271,23 +264,21 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const RunJob* jobs, int njo
 bool has_window_table(const kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t nbases, size_t msm_len) {
   const int c = merged_window(ctx, msm_len);
   if (!c) return false;
-  for (const auto& r : ctx->registered)
-    if (r.base == d_bases && r.curve == curve && r.n == nbases && r.inf == d_inf && r.table && r.table_c == c) return true;
+  size_t off = 0;
+  for (const auto& r : ctx->registered)      // the whole array, not a slice of it
+    if (covers(r, curve, d_bases, d_inf, nbases, &off) && off == 0 && r.n == nbases && r.table && r.table_c == c) return true;
   return false;
 }
 
 // window width of the table that covers [d_bases, d_bases + cnt) inside a registered array, if a merged sort of cnt scalars can use it
 // (an index slice of a host-scalar call); 0: none
 int slice_table_window(const kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t cnt) {
-  const size_t pw64 = curve == KG_G2 ? 16 : 8;
   if (cnt < ((size_t)1 << 16)) return 0;
   int s = 0;
   while (((size_t)1 << s) < cnt) ++s;
+  size_t off = 0;
   for (const auto& r : ctx->registered) {
-    if (r.curve != curve || !r.table || d_bases < r.base) continue;
-    const size_t off64 = (size_t)(d_bases - r.base);
-    if (off64 % pw64 != 0 || off64 / pw64 + cnt > r.n) continue;
-    if (d_inf != (r.inf ? r.inf + off64 / pw64 : nullptr)) continue;
+    if (!r.table || !covers(r, curve, d_bases, d_inf, cnt, &off)) continue;
     if (((size_t)r.table_W << s) > ((size_t)1 << 24)) continue;       // (window, index) must fit the entry's 24-bit field
     return r.table_c;
   }
@@ -301,14 +292,11 @@ int scalar_queue(kg_ctx* ctx, hipStream_t* out) {
 }
 
 int msm_run_multi(kg_ctx* ctx, const MsmSorted& S, int curve, const MsmRunJob* jobs, int njobs) {
-  RunJob rj[MAX_FUSED];
   if (njobs < 1 || njobs > MAX_FUSED) return KG_ERR_BAD_ARG;
-  for (int k = 0; k < njobs; ++k)
-    rj[k] = RunJob{jobs[k].d_bases, jobs[k].d_inf, jobs[k].nbases, jobs[k].idx_off, jobs[k].slot, jobs[k].bases_complete, jobs[k].packed, jobs[k].packed64};
   switch (curve) {
-    case KG_G1: return msm_run_multi_t<G1Cfg>(ctx, S, rj, njobs);
-    case KG_GRUMPKIN: return msm_run_multi_t<GkCfg>(ctx, S, rj, njobs);
-    case KG_G2: return msm_run_multi_t<G2Cfg>(ctx, S, rj, njobs);
+    case KG_G1: return msm_run_multi_t<G1Cfg>(ctx, S, jobs, njobs);
+    case KG_GRUMPKIN: return msm_run_multi_t<GkCfg>(ctx, S, jobs, njobs);
+    case KG_G2: return msm_run_multi_t<G2Cfg>(ctx, S, jobs, njobs);
     default: return KG_ERR_BAD_ARG;
   }
 }

@@ -120,7 +120,7 @@ int msm_small_enqueue(kg_ctx* ctx, hipStream_t st, int curve, const uint64_t* d_
   uint32_t H[8];
   small_bias(c, W, H);
   for (int j = 0; j < 8; ++j) a.H.w[j] = H[j];
-  a.out = (uint64_t*)sl.host_dev;
+  a.out = (uint64_t*)sl.host.mem().dev;
   a.planes = nullptr;
   a.kt = nullptr; a.spill = nullptr; a.spill_cursor = nullptr;
   const bool kt = msm_small_kt(ctx, n);
@@ -146,13 +146,8 @@ int msm_small_enqueue(kg_ctx* ctx, hipStream_t st, int curve, const uint64_t* d_
     const size_t b_kt = kt ? (nv * 4 * (glv ? 4 : 8) + 255) & ~(size_t)255 : 0, b_cur = kt ? 512 : 0, b_spill = kt ? ((size_t)W * nv * 2 + 255) & ~(size_t)255 : 0;
     const size_t b_meta = (kt && glv) ? (nv + 255) & ~(size_t)255 : 0;
     const size_t bytes = b_planes + b_kt + b_cur + b_spill + b_meta;
-    if (bytes > ctx->ws_small_bytes[slot]) {
-      if (ctx->ws_small[slot]) { sync_all(ctx); (void)hipFree(ctx->ws_small[slot]); ctx->ws_small[slot] = nullptr; ctx->ws_small_bytes[slot] = 0; }
-      const hipError_t e = dev_alloc(ctx, &ctx->ws_small[slot], bytes);
-      if (e != hipSuccess) return set_err(ctx, KG_ERR_OOM, "short-input plane buffer", e);
-      ctx->ws_small_bytes[slot] = bytes;
-    }
-    char* ws = (char*)ctx->ws_small[slot];
+    KG_TRY(ctx->ws_small[slot].ensure(DevMem{ctx, "short-input plane buffer"}, bytes));
+    char* ws = ctx->ws_small[slot].as<char>();
     a.planes = (uint32_t*)ws;
     if (kt) { a.kt = (const uint32_t*)(ws + b_planes); a.spill_cursor = (uint32_t*)(ws + b_planes + b_kt); a.spill = (uint16_t*)(ws + b_planes + b_kt + b_cur); }
     if (kt && glv) a.meta = (const uint8_t*)(ws + b_planes + b_kt + b_cur + b_spill);

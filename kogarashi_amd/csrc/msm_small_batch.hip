@@ -133,15 +133,6 @@ bool batch_shape(const kg_ctx* ctx, int curve, size_t n, MsmBatchShape* sh) {
   return true;
 }
 
-int ensure_batch_ws(kg_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->ws_small_batch_bytes) return KG_OK;
-  if (ctx->ws_small_batch) { sync_all(ctx); (void)hipFree(ctx->ws_small_batch); ctx->ws_small_batch = nullptr; ctx->ws_small_batch_bytes = 0; }   // ws_small's rule
-  const hipError_t e = dev_alloc(ctx, &ctx->ws_small_batch, bytes);
-  if (e != hipSuccess) return set_err(ctx, KG_ERR_OOM, "batched short-input scratch", e);
-  ctx->ws_small_batch_bytes = bytes;
-  return KG_OK;
-}
-
 // outside the batched kernels' lengths: one blocking kg_commit per vector, the points and flags copied to the device behind them
 int batch_fallback(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n, size_t count, size_t stride,
                    uint64_t* d_out_xy, uint8_t* d_out_inf) {
@@ -178,7 +169,7 @@ int kg_commit_batch(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8
   if (!batch_shape(ctx, curve, n, &sh)) return batch_fallback(ctx, curve, d_bases, d_inf, d_scalars, n, count, stride, d_out_xy, d_out_inf);
   KG_HIP(ctx, hipSetDevice(ctx->device));
   const size_t vb = msm_batch_vector_bytes(sh), per = msm_batch_per_launch(vb), groups = msm_batch_groups(per, count);
-  KG_TRY(ensure_batch_ws(ctx, msm_batch_scratch_bytes(vb, count)));
+  KG_TRY(ctx->ws_small_batch.ensure(DevMem{ctx, "batched short-input scratch"}, msm_batch_scratch_bytes(vb, count)));
   const int W = msm_batch_windows(sh);
   SmallArgs a;
   a.bases = d_bases; a.inf = d_inf; a.scalars = d_scalars; a.nr = (uint32_t)n; a.n = (uint32_t)(sh.glv ? 2 * n : n); a.glv = sh.glv ? 1 : 0; a.npl = sh.glv ? 4 : 8;
@@ -197,7 +188,7 @@ int kg_commit_batch(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8
     a.scalars = d_scalars + grp.first * stride * 4;
     uint64_t* oxy = d_out_xy + grp.first * pw;
     uint8_t* oinf = d_out_inf + grp.first;
-    char* ws = (char*)ctx->ws_small_batch;
+    char* ws = ctx->ws_small_batch.as<char>();
     if (curve == KG_G1) KG_TRY((batch_group<Fq, FrParams>(ctx, st, a, sh, stride, grp.count, ws, oxy, oinf)));
     else if (curve == KG_GRUMPKIN) KG_TRY((batch_group<Fr, FqParams>(ctx, st, a, sh, stride, grp.count, ws, oxy, oinf)));
     else KG_TRY((batch_group<Fq2, FrParams>(ctx, st, a, sh, stride, grp.count, ws, oxy, oinf)));

@@ -221,10 +221,10 @@ int msm_sort_begin(kg_ctx* ctx, int scalar_field, const uint64_t* d_scalars, siz
   // of d_scalars), or -- stream semantics -- for everything enqueued on the main queue so far, unless the context's inputs
   // are declared complete (kg_ctx_set_inputs_complete); and for the last reader of the set it is about to overwrite.
   const int set = (int)(ctx->sort_seq++ & 1u);
-  KG_TRY(ensure_ws_sort(ctx, set, cv.off));
-  KG_TRY(ensure_pinned(ctx, 4096));
+  KG_TRY(ctx->ws_sort[set].ensure(DevMem{ctx, "workspace allocation"}, cv.off, cv.off / 8));
+  KG_TRY(ctx->h_pinned.ensure(PinMem{ctx, "pinned staging"}, 4096));
   KG_TRY(make_sort_stream(ctx));
-  char* ws = (char*)ctx->ws_sort[set];
+  char* ws = ctx->ws_sort[set].as<char>();
   // on_main: the conversion runs on the main queue (a blocking call whose first window group is sorted and accumulated there:
   // no cross-queue hand-over in front of the first accumulation); the scalar queue is put behind it by the caller
   hipStream_t st = on_main ? ctx->stream : ctx->sort_stream;
@@ -389,7 +389,7 @@ int msm_sort_group(kg_ctx* ctx, const MsmSortPlan& Q, int g, MsmSorted* S, bool 
       hipLaunchKernelGGL(k_bucket_fill, dim3(Wg, nsplit), dim3(BR_NT), 0, st, S->bsize, B, T, nsplit, bpart, S->bstart, S->lcnt, S->lrel, rowtot, T_top, top_w);
     } else
       hipLaunchKernelGGL(k_bucket_rows, dim3(Wg), dim3(BR_NT), 0, st, S->bsize, B, T, S->bstart, S->lcnt, S->lrel, rowtot, misc, lenh, T_top, top_w, S->hot_list, HOT_MAX);
-    hipLaunchKernelGGL(k_task_bases, dim3(1), dim3(64), 0, st, rowtot, Wg, S->lbase, misc, misc + 4, lenh, lenh + LEN_BINS, (uint32_t*)ctx->h_pinned_dev + 4 * gi);
+    hipLaunchKernelGGL(k_task_bases, dim3(1), dim3(64), 0, st, rowtot, Wg, S->lbase, misc, misc + 4, lenh, lenh + LEN_BINS, (uint32_t*)ctx->h_pinned.mem().dev + 4 * gi);
     KG_HIP(ctx, hipEventRecord(ctx->ev_info[gi], st));
     hipLaunchKernelGGL(k_len_scatter, dim3(g1024), dim3(1024), 0, st, S->bsize, S->lcnt, S->lrel, S->lbase, npts, B, T, lenh + LEN_BINS, S->task_bkt, S->task_id, T_top, top_w);
     // rows of segment walkers per window; the top window (top_w >= 0: this group holds it, the sort is not merged) gets three more sets
@@ -426,7 +426,7 @@ int msm_sort(kg_ctx* ctx, int scalar_field, const uint64_t* d_scalars, size_t n,
 int msm_sort_wait(kg_ctx* ctx, MsmSorted* S) {
   KG_HIP(ctx, hipEventSynchronize(ctx->ev_info[S->group]));
   host_trace("sort: info back");
-  const uint32_t* h_info = (const uint32_t*)ctx->h_pinned + 4 * S->group;
+  const uint32_t* h_info = ctx->h_pinned.as<const uint32_t>() + 4 * S->group;
   S->ntasks = h_info[0];
   S->max_cnt = h_info[3];                              // most tasks any bucket has
   S->nhot = h_info[2];                                 // buckets with more than GATHER_SUM_MAX tasks (listed up to HOT_MAX)

@@ -241,8 +241,8 @@ int kg_ntt_bn254_fr(kg_ctx* ctx, uint64_t* d_data, uint32_t log_n, int inverse, 
   KG_HIP(ctx, hipSetDevice(ctx->device));
   uint64_t* tmp = nullptr;
   if (log_n > (uint32_t)NTT_MAX_LOG_M) {
-    KG_TRY(ensure_ws2(ctx, ((size_t)1 << log_n) * 32));
-    tmp = (uint64_t*)ctx->ws2;
+    KG_TRY(ctx->ws2.ensure(DevMem{ctx, "ntt buffer allocation"}, ((size_t)1 << log_n) * 32));
+    tmp = ctx->ws2.as<uint64_t>();
   }
   return kg::ntt_enqueue(ctx, ctx->stream, tmp, d_data, log_n, inverse, coset);
   });

@@ -82,8 +82,8 @@ int kg_ntt_bn254_fr_batch(kg_ctx* ctx, uint64_t* d_data, uint32_t log_n, size_t 
   const int nsteps = ntt_plan(log_n, tuning().ntt_steps, d, tuning().ntt_tile);    // the plan the tables were built for (ntt.hip)
   uint64_t* tmp = nullptr;
   if (nsteps > 1) {
-    KG_TRY(ensure_ws2(ctx, ntt_batch_scratch_elems(log_n, count) * 32));
-    tmp = (uint64_t*)ctx->ws2;
+    KG_TRY(ctx->ws2.ensure(DevMem{ctx, "ntt buffer allocation"}, ntt_batch_scratch_elems(log_n, count) * 32));
+    tmp = ctx->ws2.as<uint64_t>();
   }
   const size_t per = ntt_batch_per_launch(log_n), groups = ntt_batch_groups(log_n, count);
   hipStream_t st = ctx->stream;

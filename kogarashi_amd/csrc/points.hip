@@ -46,12 +46,6 @@ __global__ void __launch_bounds__(64) k_points_check(const uint64_t* __restrict_
     summary_add(summary, (unsigned long long)__popcll(bad), (unsigned long long)blockIdx.x * 64 + (unsigned long long)(__ffsll((long long)bad) - 1));
 }
 
-int ensure_ws_points(kg_ctx* c) {
-  if (c->ws_points) return KG_OK;
-  KG_HIP(c, dev_alloc(c, &c->ws_points, WS_BYTES));
-  return KG_OK;
-}
-
 template <class F, bool SUB>
 void launch_check(kg_ctx* c, const uint64_t* xy, const uint8_t* inf, size_t n, uint8_t* status, unsigned long long* summary) {
   hipLaunchKernelGGL((k_points_check<F, SUB>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, xy, inf, n, status, summary);
@@ -66,8 +60,8 @@ int run_check(kg_ctx* c, int curve, const uint64_t* d_xy, const uint8_t* d_inf, 
     return KG_OK;
   }
   if (n >= ((size_t)1 << 37)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^37 points");       // the grid's x dimension
-  KG_TRY(ensure_ws_points(c));
-  unsigned long long* summary = (unsigned long long*)c->ws_points;
+  KG_TRY(c->ws_points.ensure(DevMem{c, "point-check work space"}, WS_BYTES));
+  unsigned long long* summary = c->ws_points.as<unsigned long long>();
   hipLaunchKernelGGL(k_summary_init<unsigned long long>, dim3(1), dim3(1), 0, c->stream, summary, (unsigned long long)n, (uint32_t*)nullptr);
   const bool sub = (checks & KG_CHECK_SUBGROUP) != 0;
   if (curve == KG_G1) launch_check<Fq, false>(c, d_xy, d_inf, n, d_status, summary);
@@ -104,15 +98,15 @@ int kg_groth16_crs_check(kg_ctx* c, const kg_groth16_crs* crs, int checks, size_
   for (int k = 0; k < 10; ++k) out_bad[k] = 0;
   for (int k = 0; k < 5; ++k) KG_TRY(run_check(c, dev[k].curve, dev[k].xy, dev[k].inf, dev[k].n, checks, nullptr, &out_bad[k], nullptr));
   // the five host points, through a small device buffer of the context
-  KG_TRY(ensure_ws_points(c));
+  KG_TRY(c->ws_points.ensure(DevMem{c, "point-check work space"}, WS_BYTES));
   uint64_t h_xy[WS_HOST_XY / 8];
   uint8_t h_inf[16] = {0};
   for (int i = 0; i < 8; ++i) { h_xy[i] = crs->alpha_g1[i]; h_xy[8 + i] = crs->beta_g1[i]; h_xy[16 + i] = crs->delta_g1[i]; }
   for (int i = 0; i < 16; ++i) { h_xy[24 + i] = crs->beta_g2[i]; h_xy[40 + i] = crs->delta_g2[i]; }
   h_inf[2] = crs->delta_g1_inf;
   h_inf[4] = crs->delta_g2_inf;
-  uint64_t* d_xy = (uint64_t*)((char*)c->ws_points + WS_SUMMARY);
-  uint8_t* d_inf = (uint8_t*)c->ws_points + WS_SUMMARY + WS_HOST_XY;
+  uint64_t* d_xy = (uint64_t*)(c->ws_points.as<char>() + WS_SUMMARY);
+  uint8_t* d_inf = c->ws_points.as<uint8_t>() + WS_SUMMARY + WS_HOST_XY;
   KG_HIP(c, hipMemcpyAsync(d_xy, h_xy, sizeof h_xy, hipMemcpyHostToDevice, c->stream));
   KG_HIP(c, hipMemcpyAsync(d_inf, h_inf, sizeof h_inf, hipMemcpyHostToDevice, c->stream));
   KG_HIP(c, hipStreamSynchronize(c->stream));

@@ -172,10 +172,10 @@ int kg_groth16_setup_bn254(kg_ctx* ctx, const kg_csr* a, const kg_csr* b, const 
                o_ics = cv.take((l + 1) * 32), o_ls = cv.take((m_l_1 + 1) * 32), o_cnt = cv.take((nv + 2) * 4), o_cur = cv.take((nv + 2) * 4),
                o_tptr = cv.take((nv + 2) * 8), o_tcol = cv.take((nnz_max + 1) * 8), o_tval = cv.take((nnz_max + 1) * 32),
                o_vks = cv.take(6 * 32), o_vk1 = cv.take(3 * 64), o_vk2 = cv.take(3 * 128), o_vki = cv.take(64);
-  char* ws = nullptr;
-  if (hipError_t e = dev_alloc(ctx, (void**)&ws, cv.off); e != hipSuccess) return set_err(ctx, KG_ERR_OOM, "setup scratch allocation", e);
-  struct Free { kg_ctx* c; char* p; ~Free() { kg_ctx_sync(c); hipFree(p); } } guard{ctx, ws};
-  KG_TRY(ensure_ws_vec(ctx, RowWs::bytes(nv)));
+  DevBuf scratch;
+  KG_TRY(scratch.ensure(DevMem{ctx, "setup scratch allocation"}, cv.off));
+  char* const ws = scratch.as<char>();
+  KG_TRY(ctx->ws_vec.ensure(DevMem{ctx, "workspace allocation"}, RowWs::bytes(nv)));
   hipStream_t st = ctx->stream;
   uint64_t* pw = (uint64_t*)(ws + o_pw);
   uint64_t* h_s = (uint64_t*)(ws + o_hs);
@@ -219,7 +219,7 @@ int kg_groth16_setup_bn254(kg_ctx* ctx, const kg_csr* a, const kg_csr* b, const 
       hipLaunchKernelGGL(k_transpose_fill, dim3((unsigned)((nnz[j] + 255) / 256)), dim3(256), 0, st, mats[j]->d_row_ptr, mats[j]->d_col, mats[j]->d_val, m, nnz[j],
                          cursor, t_col, t_val);
     KG_HIP(ctx, hipGetLastError());
-    KG_TRY(r1cs_prod_enqueue(ctx, st, KG_FR, t_ptr, t_col, t_val, nv, pw, ev[j], RowWs(ctx->ws_vec, nv)));
+    KG_TRY(r1cs_prod_enqueue(ctx, st, KG_FR, t_ptr, t_col, t_val, nv, pw, ev[j], RowWs(ctx->ws_vec.get(), nv)));
   }
   if (nv) {
     // (beta * at + alpha * bt + ct) * inv, inv = 1/gamma for the l instance wires and 1/delta for the witness wires (zksnark.rs:180-187)

@@ -501,8 +501,8 @@ int kg_r1cs_prod(kg_ctx* c, int field, const uint64_t* row_ptr, const uint64_t* 
   if (!row_ptr || !col || !val || !z || !out) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
-  KG_TRY(ensure_ws_vec(c, RowWs::bytes(m)));
-  return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, out, RowWs(c->ws_vec, m));
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, out, RowWs(c->ws_vec.get(), m));
 }
 
 int kg_r1cs_evaluate(kg_ctx* c, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z, uint64_t* out) {
@@ -517,8 +517,8 @@ int kg_nova_cross_term(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, c
   KG_HIP(c, hipSetDevice(c->device));
   const Limbs9 u1 = scaled(h_u1, field == KG_FR), u2 = scaled(h_u2, field == KG_FR);
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
-  KG_TRY(ensure_ws_vec(c, RowWs::bytes(m)));
-  const RowWs ws(c->ws_vec, m);
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  const RowWs ws(c->ws_vec.get(), m);
   KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, c->stream));
   by_field(field, [&](auto p) { launch_rows(c->stream, CrossOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z1, d_z2, u1, u2, d_out}, m, ws); });
   KG_HIP(c, hipGetLastError());
@@ -538,8 +538,8 @@ int kg_r1cs_check(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const 
   KG_HIP(c, hipSetDevice(c->device));
   const bool fr = field == KG_FR;
   const Limbs9 us = scaled(h_u ? h_u : (fr ? HostFrP::ONE : HostFqP::ONE), fr);       // no u: the plain relation, u = 1
-  KG_TRY(ensure_ws_vec(c, RowWs::bytes(m)));
-  const RowWs ws(c->ws_vec, m);
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  const RowWs ws(c->ws_vec.get(), m);
   hipLaunchKernelGGL(k_summary_init<uint32_t>, dim3(1), dim3(1), 0, c->stream, ws.summary, (uint32_t)m, ws.count);
   by_field(field, [&](auto p) { launch_rows(c->stream, CheckOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z, us, d_e, d_status}, m, ws); });
   KG_HIP(c, hipGetLastError());
