@@ -300,6 +300,27 @@ class Prover:
                     pass
 
 
+    def create_proofs_batch(self, jobs):
+        """Proofs for a list of (a_eval, b_eval, c_eval, x, w, r, s) of this circuit in ONE call (kg_groth16_prove_batch): the inputs are
+        uploaded as packed arrays, every launch is shared by a group of proofs and the assembly runs on the device.  Returns
+        (proofs, flags): arrays of shape (count, 32) -- A (8) | B (16) | C (8) words -- and (count, 3); proof b equals
+        create_proof(*jobs[b]) bit for bit.  Raises KogarashiError (unsupported) for circuits whose MSMs are longer than the batched
+        short MSM takes (lib.groth16_prove_batch_plan == (0, 0)): create_proofs is the loop for those."""
+        jobs = list(jobs)
+        count = len(jobs)
+        if count == 0:
+            return np.zeros((0, 32), dtype=np.uint64), np.zeros((0, 3), dtype=np.uint8)
+        pack = lambda k, n: np.ascontiguousarray(np.stack([np.asarray(j[k], dtype=np.uint64).reshape(-1, 4)[:n].reshape(n, 4) for j in jobs]))
+        up = lambda a: self.ctx.upload(a if a.size else np.zeros((1, 4), dtype=np.uint64))
+        da, db, dc = up(pack(0, self.m)), up(pack(1, self.m)), up(pack(2, self.m))
+        dx, dw = up(pack(3, self.l)), up(pack(4, self.m_l_1))
+        dr, ds = up(pack(5, 1)), up(pack(6, 1))
+        d_out, d_inf = self.ctx.empty((count, 32)), self.ctx.empty((count, 3), dtype=np.uint8)
+        self.ctx.groth16_prove_batch(self.crs, da.ptr, db.ptr, dc.ptr, self.m, dx.ptr, self.l, dw.ptr if self.m_l_1 else 0, self.m_l_1,
+                                     dr.ptr, ds.ptr, count, d_out.ptr, d_inf.ptr)
+        return d_out.numpy(), d_inf.numpy()      # (kg_memcpy_d2h follows the stream)
+
+
 class ShardedProver:
     """groth16::Prover over several contexts (normally one per GPU), task-parallel: SURVEY.md 8e -- the MSMs of
     prover.rs:51-65 are independent until the assembly and the G2 query is the long pole.  Context 0 holds b_g2 and runs

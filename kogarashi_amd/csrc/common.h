@@ -138,7 +138,8 @@ struct kg_ctx {
   Slot slots[NSLOTS];
   kg::DevBuf ws_small[NSLOTS];           // short-input MSM (msm_small.hip): plane points of a window split over several workgroups, per result slot
   kg::DevBuf ws_small_batch;             // batched short-input MSM (msm_small_batch.hip): window sums and plane points of one launch group
-  std::unique_ptr<kg::WorkerPool> workers;   // host worker threads (worker_pool.h), started on demand, alive until the context is destroyed
+  kg::DevBuf ws_g16_batch;               // batched prover (groth16_batch.hip): polynomials, z, sums and chain results of one launch group
+  std::unique_ptr<kg::WorkerPool> workers;  // host worker threads (worker_pool.h), started on demand, alive until the context is destroyed
   std::shared_ptr<void> prover_jobs;     // groth16.hip: proofs in flight (kg_groth16_prove_begin / _end)
   size_t ticket_n[4] = {0, 0, 0, 0};     // lengths of the MSMs begun with kg_msm_begin
   // kg_msm_begin starts the ticket's host finish (wait for the reduction, 255-step double-and-add, inversion) on a worker

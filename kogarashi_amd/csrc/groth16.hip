@@ -11,6 +11,7 @@
 #include <chrono>
 #include <cstdlib>
 #include "host_fp.h"
+#include "groth16_qap.h"
 #include <future>
 #include <vector>
 #include <type_traits>
@@ -78,20 +79,6 @@ __global__ void __launch_bounds__(64) k_fixed_base_mul(const uint64_t* __restric
     put_ref(F::one(), dst + E64);
     out_inf[i] = 1;
   }
-}
-
-// h[i] = (a[i] * b[i] - c[i]) * zinv   (poly.rs:168-195 + fft.rs:150-154 in one pass; data stays in ABI form)
-__global__ void __launch_bounds__(256) k_qap_combine(uint64_t* __restrict__ a, const uint64_t* __restrict__ b, const uint64_t* __restrict__ c,
-                                                     size_t n, Words8 zinv) {
-  KG_SERVICE_PRIO();
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint32_t wa[8], wb[8], wc[8], wo[8];
-  load_words(a, i, wa); load_words(b, i, wb); load_words(c, i, wc);
-  Fr x = from_ref<FrParams>(wa), y = from_ref<FrParams>(wb), z = from_ref<FrParams>(wc);
-  Fr t = norm(sub<4, 1>(mul(x, y), z));
-  to_ref(mul(t, from_ref<FrParams>(zinv.w)), wo);
-  store_words(a, i, wo);
 }
 
 // ---- host curve helpers (assembly of the proof, prover.rs:71-98) ---------------------------------------
@@ -527,16 +514,7 @@ int prove_enqueue(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_t* d_a_ev
   }
   auto h_front = [&]() {                                  // h = (a o b - c) / Z on the coset, back to coefficients (prover.rs:43-47)
     for (int v = 1; v < 3; ++v) hip_rc(hipStreamWaitEvent(hq, ctx->ev_join[v], 0), "hipStreamWaitEvent(join)");   // chain 0 shares chain 2's queue, in front of it
-    HostFr seven = HostFr::one();                         // (7^n - 1)^-1 on the host: n = 2^k squarings of 7
-    {
-      HostFr one = HostFr::one(), acc = HostFr::zero();
-      for (int i = 0; i < 7; ++i) acc = add(acc, one);
-      seven = acc;
-    }
-    HostFr z = seven;
-    for (uint32_t i = 0; i < k; ++i) z = sqr(z);
-    z = inv(sub<4, 1>(z, HostFr::one()));                 // z_on_coset().invert() (fft.rs:141-151)
-    hipLaunchKernelGGL(k_qap_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hq, A, B, C, n, words8(z.v));
+    hipLaunchKernelGGL(k_qap_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hq, A, B, C, n, qap_zinv(k));   // (7^n - 1)^-1 on the host
     hip_rc(hipGetLastError(), "k_qap_combine launch");
     if (rc == KG_OK) rc = ntt_enqueue(ctx, hq, TMP, A, k, 1, 1);             // coset_idft (prover.rs:47)
   };

@@ -61,6 +61,7 @@
   X(g16_blind_early, "KG_G16_BLIND_EARLY", 1, "a proof's blinding chains (prover.rs:75-77, three 255-step host chains) start when the proof is enqueued; 0 = when its assembly starts") \
   X(g16_small_h_first, "KG_G16_SMALL_H_FIRST", 4096, "a short proof (one-launch MSMs) with more witness entries than this issues h's whole chain before the three G1 witness MSMs") \
   X(g16_h_inline, "KG_G16_H_INLINE", 1, "a blocking proof runs h's reduction behind h's accumulation on the main queue") \
+  X(g16_batch_mb, "KG_G16_BATCH_MB", 256, "MiB of scratch one launch group of kg_groth16_prove_batch may take, 1..4096 (values outside are clamped): a group carries min(count, cap / scratch bytes per proof) proofs, at least one") \
   /* ---- NTT ------------------------------------------------------------------------------------------------------------------------- */ \
   X(ntt_direct_max_log, "KG_NTT_DIRECT_MAX_LOG", 22, "largest log2 of a direct inter-step twiddle table, 0..22 (beyond it, and when the allocation fails: composed twiddles)") \
   X(ntt_steps, "KG_NTT_STEPS", 0, "force the number of steps (HBM round trips) of a transform, 1..3; 0 = by size") \

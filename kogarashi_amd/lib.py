@@ -34,6 +34,7 @@ EXPORTS = [
     "kg_points_check", "kg_groth16_crs_check", "kg_r1cs_check",
     "kg_ntt_bn254_fr_batch", "kg_fr_divide_by_z_on_coset_batch", "kg_ntt_batch_plan",
     "kg_commit_batch", "kg_commit_batch_plan",
+    "kg_groth16_prove_batch", "kg_groth16_prove_batch_plan",
 ]
 
 
@@ -108,6 +109,11 @@ def load():
         _lib.kg_commit_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
         _lib.kg_commit_batch_plan.restype = C.c_int
         _lib.kg_commit_batch_plan.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
+        _lib.kg_groth16_prove_batch.restype = C.c_int
+        _lib.kg_groth16_prove_batch.argtypes = [C.c_void_p, C.POINTER(Groth16Crs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        _lib.kg_groth16_prove_batch_plan.restype = C.c_int
+        _lib.kg_groth16_prove_batch_plan.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
     return _lib
 
 
@@ -147,6 +153,15 @@ def commit_batch_plan(curve: int, n: int, count: int) -> tuple[int, int]:
     (no device needed)"""
     per = C.c_size_t(0)
     groups = int(load().kg_commit_batch_plan(int(curve), C.c_size_t(n), C.c_size_t(count), C.byref(per)))
+    return groups, int(per.value)
+
+
+def groth16_prove_batch_plan(m: int, l: int, m_l_1: int, count: int) -> tuple[int, int]:
+    """kg_groth16_prove_batch_plan: (launch groups a batch of `count` proofs of an (m, l, m_l_1) circuit is cut into, proofs of a full
+    group); (0, 0) for count == 0 and for circuits kg_groth16_prove_batch refuses -- an MSM length outside the batched short MSM's
+    (no device needed)"""
+    per = C.c_size_t(0)
+    groups = int(load().kg_groth16_prove_batch_plan(C.c_size_t(m), C.c_size_t(l), C.c_size_t(m_l_1), C.c_size_t(count), C.byref(per)))
     return groups, int(per.value)
 
 
@@ -463,6 +478,17 @@ class Context:
             raise ProverSubVersionCrsAttack("delta is the identity")
         self._chk(rc, "kg_groth16_prove_bn254")
         return out[:8].copy(), out[8:24].copy(), out[24:].copy(), inf
+
+    def groth16_prove_batch(self, crs: "Groth16Crs", a_eval: int, b_eval: int, c_eval: int, eval_stride: int, x: int, x_stride: int, w: int, w_stride: int,
+                            r: int, s: int, count: int, proofs: int, proof_inf: int):
+        """kg_groth16_prove_batch: count proofs of one circuit; every argument is a device pointer or a stride in elements (proof b reads
+        element b * stride of its arrays and 4 words at r + 4 b, s + 4 b; writes 32 words and 3 flags).  Enqueued on the context's
+        stream: the outputs are valid in stream order or after sync()."""
+        rc = self._lib.kg_groth16_prove_batch(self._h, C.byref(crs), _vp(a_eval), _vp(b_eval), _vp(c_eval), C.c_size_t(eval_stride), _vp(x), C.c_size_t(x_stride),
+                                              _vp(w), C.c_size_t(w_stride), _vp(r), _vp(s), C.c_size_t(count), _vp(proofs), _vp(proof_inf))
+        if rc == -6:
+            raise ProverSubVersionCrsAttack("delta is the identity")
+        self._chk(rc, "kg_groth16_prove_batch")
 
     def groth16_prove_begin(self, crs: "Groth16Crs", a_eval: int, b_eval: int, c_eval: int, x: int, w: int, r: np.ndarray, s: np.ndarray, ticket: int):
         """kg_groth16_prove_begin: enqueue a proof (ticket 0 or 1); crs and the device inputs stay alive until the end."""
