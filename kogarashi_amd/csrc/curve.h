@@ -86,22 +86,37 @@ KG_HD XYZZ<F> add_mixed(const XYZZ<F>& p, const Affine<F>& a) {
   return {x3, y3, mul(p.zz, pp), mul(p.zzz, ppp)};
 }
 
+// A base gathered in the ABI form (fp29.h limbs_from_words_x32: K = 32) -> the internal form, both coordinates < 2p with
+// the limbs k_prep_bases would have stored.  Only the paths that use a.x / a.y as VALUES call it (below).
+template <class F>
+KG_HD Affine<F> affine_from_abi(const Affine<F>& a) { return {from_ref_x32(a.x), from_ref_x32(a.y)}; }
+
 // P + (+-a): the bucket kernel's form.  The sign of a signed digit is folded into R = +-S2 - Y1 (a fat subtraction
 // from zero: 8p - S2) instead of negating the point's y first (subtract, normalise, value-reduce: ~80 instructions that
 // every lane of a wave pays as soon as one lane's digit is negative).
 // (Base fields only: R reaches K = 12 in the negated case, which an Fq2 square's inner subtraction does not admit --
 // the Fq2 overload below negates the point as before.)
+// abi (wave-uniform in the kernel): a.x, a.y are K = 32 operands.  The main path uses them only in the two products below --
+// U2, S2 < (32 * 2 / 169 + 1) p = 1.38p, inside the bounds the subtractions are written for (U2, S2 < 2.1p) -- so nothing
+// after them changes; the three exits that take the point as a value (a first entry, a doubling, the negation of either)
+// convert it first (< 2p, as a resident base), so no K = 32 value is stored in an accumulator or reaches a sub<>.
 template <class F>
-KG_HD XYZZ<F> add_mixed_signed(const XYZZ<F>& p, const Affine<F>& a, bool negate) {
-  if (is_identity(p)) return from_affine(negate ? neg_affine(a) : a);
-  F u2 = mul(a.x, p.zz);
-  F s2 = mul(a.y, p.zzz);
+KG_HD XYZZ<F> add_mixed_signed(const XYZZ<F>& p, const Affine<F>& a, bool negate, bool abi) {
+  if (is_identity(p)) {
+    const Affine<F> b = abi ? affine_from_abi(a) : a;       // < 2p either way
+    return from_affine(negate ? neg_affine(b) : b);
+  }
+  F u2 = mul(a.x, p.zz);                // abi: K 32 * 2 -> U2 < 1.38p; else < 1.03p
+  F s2 = mul(a.y, p.zzz);               // the same for S2
   F pp_ = norm(sub<8, 1>(u2, p.x));     // P = U2 - X1   (X1 < 6p: see X3 below)
   F t = negate ? sub<8, 1>(F::zero(), s2) : s2;   // S2 < 2.1p: the 4p constant does not dominate its top limb
   F r = norm(sub<4, 1>(t, p.y));        // R = +-S2 - Y1
   F pp = sqr(pp_);
   if (is_zero_2p(pp)) {                 // same x: doubling or inverse (weierstrass.rs:75-81)
-    if (is_zero(r)) return double_affine(negate ? neg_affine(a) : a);
+    if (is_zero(r)) {
+      const Affine<F> b = abi ? affine_from_abi(a) : a;     // < 2p either way
+      return double_affine(negate ? neg_affine(b) : b);
+    }
     return XYZZ<F>::identity();
   }
   F ppp = mul(pp_, pp);
@@ -112,6 +127,8 @@ KG_HD XYZZ<F> add_mixed_signed(const XYZZ<F>& p, const Affine<F>& a, bool negate
   F y3 = mul2sub(r, norm(sub<8, 1>(q, x3)), p.y, ppp);          // R*(Q - X3) - Y1*PPP with ONE reduction
   return {x3, y3, mul(p.zz, pp), mul(p.zzz, ppp)};
 }
+template <class F>
+KG_HD XYZZ<F> add_mixed_signed(const XYZZ<F>& p, const Affine<F>& a, bool negate) { return add_mixed_signed(p, a, negate, false); }
 
 template <class G>
 KG_HD XYZZ<Fp2<G>> add_mixed_signed(const XYZZ<Fp2<G>>& p, const Affine<Fp2<G>>& a, bool negate) {

@@ -491,6 +491,33 @@ KG_HD Fp<P> limbs_from_words(const uint32_t w[8]) {
   r.l[8] = w[7] >> 8;
   return r;
 }
+// The ABI form as an operand (the accumulation's gather, msm_bases.h): 32 x the raw integer, i.e. the 5-bit offset folded into the
+// same shifts.  A reference value v = x*2^256 < p read as 32 v IS x*2^261, the internal Montgomery form, as a representative below
+// 32p: normalised limbs (the top one < 2^27), K = 32 -- admissible only as an operand of mul() against K <= 5 (32 * 5 < 169),
+// never of sub<>, and never stored.
+template <class P>
+KG_HD Fp<P> limbs_from_words_x32(const uint32_t w[8]) {
+  Fp<P> r;
+  r.l[0] = (w[0] << 5) & M29;
+  r.l[1] = ((w[0] >> 24) | (w[1] << 8)) & M29;
+  r.l[2] = ((w[1] >> 21) | (w[2] << 11)) & M29;
+  r.l[3] = ((w[2] >> 18) | (w[3] << 14)) & M29;
+  r.l[4] = ((w[3] >> 15) | (w[4] << 17)) & M29;
+  r.l[5] = ((w[4] >> 12) | (w[5] << 20)) & M29;
+  r.l[6] = ((w[5] >> 9) | (w[6] << 23)) & M29;
+  r.l[7] = ((w[6] >> 6) | (w[7] << 26)) & M29;
+  r.l[8] = w[7] >> 3;
+  return r;
+}
+// the limbs of 32 v (normalised, low five bits zero) -> the limbs of v, as limbs_from_words gives them
+template <class P>
+KG_HD Fp<P> limbs_div32(const Fp<P>& a) {
+  Fp<P> r;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r.l[i] = (a.l[i] >> 5) | ((a.l[i + 1] & 31u) << 24);
+  r.l[8] = a.l[8] >> 5;
+  return r;
+}
 // normalised limbs of a value < 2^256 -> 8 words
 template <class P>
 KG_HD void words_from_limbs(const Fp<P>& a, uint32_t w[8]) {
@@ -506,6 +533,9 @@ KG_HD void words_from_limbs(const Fp<P>& a, uint32_t w[8]) {
 // reference Montgomery form (x*2^256) -> internal (x*2^261), normalised, < 2p
 template <class P>
 KG_HD Fp<P> from_ref(const uint32_t w[8]) { return mul(limbs_from_words<P>(w), Fp<P>::from_const(P::C_FROM_REF)); }
+// the same from the x32 limbs of the reference value (limbs_from_words_x32): K = 32 in, the limbs and the value (< 2p) of from_ref out
+template <class P>
+KG_HD Fp<P> from_ref_x32(const Fp<P>& a) { return mul(limbs_div32(a), Fp<P>::from_const(P::C_FROM_REF)); }
 // internal -> reference form, canonical
 template <class P>
 KG_HD void to_ref(const Fp<P>& a, uint32_t w[8]) {

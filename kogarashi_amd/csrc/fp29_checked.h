@@ -194,6 +194,23 @@ inline FpChecked<P> inv(const FpChecked<P>& a) {
   return {inv(a.v), (double)M29, 2.0 * FpChecked<P>::ptop1(), 2.0};
 }
 
+// the ABI form as an operand (fp29.h limbs_from_words_x32): the caller vouches for a canonical reference value (< p), so 32 v < 32p
+template <class P>
+inline FpChecked<P> checked_from_words_x32(const uint32_t w[8]) {
+  FpChecked<P> r{limbs_from_words_x32<P>(w), (double)M29, 32.0 * FpChecked<P>::ptop1(), 32.0};
+  r.check_actual();
+  return r;
+}
+template <class P>
+inline FpChecked<P> from_ref_x32(const FpChecked<P>& a) {
+  a.check_actual();
+  if (!(a.lb <= (double)M29)) BoundFail::fail("from_ref_x32 input limbs not normalised", a.lb, (double)M29);
+  if (a.v.l[0] & 31u) BoundFail::fail("from_ref_x32 input is not 32 x a value", a.v.l[0] & 31u, 0);
+  const FpChecked<P> v{limbs_div32(a.v), (double)M29, a.tb / 32.0, a.kb / 32.0};
+  v.check_actual();
+  return mul(v, FpChecked<P>::from_const(P::C_FROM_REF));
+}
+
 template <class P>
 inline FpChecked<P> inv_fast(const FpChecked<P>& a) { return inv(a); }      // same value; the binary GCD has no column bounds to track
 

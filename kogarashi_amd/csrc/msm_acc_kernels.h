@@ -82,13 +82,19 @@ struct PointAoS<Fp2S<G>> {
 // wave slots -- one round, no refill, and a tail at one wave per SIMD (69 % of the four-wave issue rate); three arrays
 // make 3.2 rounds (measured: 10.2 -> 13 G additions/s).
 constexpr int MAX_FUSED = 3;
+// how the points of a base array lie in memory (one code per array, so the branch on it is uniform over a wave)
+enum : uint8_t {
+  BASES_72 = 0,     // resident limb form (BaseIO::load_point)
+  BASES_64 = 1,     // resident 64-byte form (BaseIO::load_point64)
+  BASES_ABI = 2     // the caller's own array, gathered as it is (BaseIO::load_point_abi): base-field curves, no identity flags
+};
 struct AccSets {
   int nsets;
   const uint32_t* pb[MAX_FUSED];      // packed bases of each array
   uint32_t idx_off[MAX_FUSED];        // scalars in front of the array (shared sort, z = x || w)
   uint32_t* partial[MAX_FUSED];       // partial sums, one per task
   uint32_t tab_n[MAX_FUSED];          // merged sort: points per window of the array's table (pb = the table)
-  uint8_t fmt64[MAX_FUSED];           // the array is in the 64-byte resident form (BaseIO::load_point64)
+  uint8_t fmt[MAX_FUSED];             // BASES_72 / BASES_64 / BASES_ABI
 };
 // G2: the compiler lands on 256 VGPRs + 1 AGPR = one wave per SIMD; asking for two waves costs a few spilled registers
 // and buys the second wave (the issue rate of this code at one wave per SIMD is ~69 % of its rate at four)
@@ -120,11 +126,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AccWave
   if (p >= L.base[W]) return;
   const uint32_t* __restrict__ pbases = A.pb[0];
   uint32_t idx_off = A.idx_off[0], tab_n = A.tab_n[0];
-  bool fmt64 = A.fmt64[0] != 0;
+  uint32_t fmt = A.fmt[0];
   uint32_t* __restrict__ partial = A.partial[0];
 #pragma unroll
   for (int k = 1; k < MAX_FUSED; ++k)
-    if (set == k) { pbases = A.pb[k]; idx_off = A.idx_off[k]; partial = A.partial[k]; tab_n = A.tab_n[k]; fmt64 = A.fmt64[k] != 0; }
+    if (set == k) { pbases = A.pb[k]; idx_off = A.idx_off[k]; partial = A.partial[k]; tab_n = A.tab_n[k]; fmt = A.fmt[k]; }
   const size_t bi = task_bkt[p];
   const uint32_t t = task_id[p];
   const int w = (int)(bi / B);
@@ -147,9 +153,18 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AccWave
 #else
     const size_t at = row + (idx - idx_off);
 #endif
-    if (fmt64 ? BaseIO<F>::load_point64(pbases + at * (2 * BaseIO<F>::PK), a.x, a.y) : BaseIO<F>::load_point(pbases + at * PW, a.x, a.y))
-      continue;                                          // identity base (msm.rs:58-64 adds it as a no-op)
-    acc = add_mixed_signed(acc, a, (e & 0x80000000u) != 0);
+    if constexpr (BaseIO<F>::HAS_ABI) {                  // one addition body for the three forms; the form is uniform over the wave
+      const bool abi = fmt == BASES_ABI;
+      bool inf = false;
+      if (abi) BaseIO<F>::load_point_abi(pbases + at * 16, a.x, a.y);      // the caller's array as it is: K = 32 operands, never an identity
+      else inf = fmt == BASES_64 ? BaseIO<F>::load_point64(pbases + at * (2 * BaseIO<F>::PK), a.x, a.y) : BaseIO<F>::load_point(pbases + at * PW, a.x, a.y);
+      if (inf) continue;                                 // identity base (msm.rs:58-64 adds it as a no-op)
+      acc = add_mixed_signed(acc, a, (e & 0x80000000u) != 0, abi);
+    } else {
+      if (fmt == BASES_64 ? BaseIO<F>::load_point64(pbases + at * (2 * BaseIO<F>::PK), a.x, a.y) : BaseIO<F>::load_point(pbases + at * PW, a.x, a.y))
+        continue;
+      acc = add_mixed_signed(acc, a, (e & 0x80000000u) != 0);
+    }
   }
   AccStore<F>::store(partial, t, acc);
 }
@@ -248,7 +263,7 @@ static int acc_prefetch(const AccSets& A, int njobs, size_t nbases) {
   const int mode = tuning().acc_prefetch, from_log = tuning().acc_prefetch_log;
   if (mode == 0 || nbases < ((size_t)1 << from_log)) return 0;
   for (int k = 0; k < njobs; ++k)
-    if (!A.fmt64[k]) return 0;
+    if (A.fmt[k] != BASES_64) return 0;
   return mode;
 }
 #endif      // KG_EXPERIMENTS

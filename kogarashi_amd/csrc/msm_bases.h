@@ -1,5 +1,6 @@
 // msm_bases.h -- resident form of the bases (72-byte limb points or 64-byte packed points, identity flag in a spare bit), their
-// conversion from the ABI form (k_prep_bases) and the window tables of registered arrays (k_table_next).
+// conversion from the ABI form (k_prep_bases), the gather of an unconverted array as the caller holds it (load_point_abi) and the
+// window tables of registered arrays (k_table_next).
 #pragma once
 #include "msm_common.h"
 
@@ -46,6 +47,17 @@ template <class P> struct BaseIO<Fp<P>> {
     x = limbs_from_words<P>(w); y = limbs_from_words<P>(w + 8);
     return inf;
   }
+  // The caller's own array (BASES_ABI): 64 bytes of canonical reference values x*2^256 | y*2^256, no identity flag (the caller of
+  // the kernel vouches for a null flag array).  One 64-byte read, unpacked with the factor 32 in the shifts: x, y come out as
+  // x*2^261, y*2^261 below 32p with normalised limbs -- operands of a product only (curve.h add_mixed_signed, abi = true).
+  static constexpr bool HAS_ABI = true;
+  static __device__ __forceinline__ void load_point_abi(const uint32_t* src, Fp<P>& x, Fp<P>& y) {
+    uint32_t w[16];
+    const uint4* p = reinterpret_cast<const uint4*>(src);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const uint4 v = p[j]; w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w; }
+    x = limbs_from_words_x32<P>(w); y = limbs_from_words_x32<P>(w + 8);
+  }
   // the same from the sixteen words themselves (k_acc_tasks_q reads them out of LDS)
   static __device__ __forceinline__ bool point64_from_words(uint32_t (&w)[16], Fp<P>& x, Fp<P>& y) {
     const bool inf = (w[7] & INF_BIT) != 0;
@@ -68,6 +80,7 @@ template <class P> struct BaseIO<Fp<P>> {
 template <class F> struct BaseIO<Fp2<F>> {
   static constexpr int W = 16;
   static constexpr int PE = 18;
+  static constexpr bool HAS_ABI = false;   // G2 arrays are always converted (K = 32 through the Fq2 double products is not checked)
   static __device__ __forceinline__ void convert(const uint64_t* src, uint32_t* dst) {
     BaseIO<F>::convert(src, dst);
     BaseIO<F>::convert(src + 4, dst + 9);
@@ -120,6 +133,7 @@ namespace {        // internal linkage: the kernels of a header exist once per t
 // lane exchange (both lanes of the pair always execute it).
 template <class G> struct BaseIO<Fp2S<G>> {
   static constexpr int W = 16, PE = 18, PK = 16;
+  static constexpr bool HAS_ABI = false;
   using P = typename G::Params;
   static __device__ __forceinline__ bool load_point64(const uint32_t* src, Fp2S<G>& x, Fp2S<G>& y) {
     const int h = Fp2S<G>::half();

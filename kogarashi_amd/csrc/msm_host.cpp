@@ -225,13 +225,14 @@ static int msm_grouped(kg_ctx* ctx, int curve, const uint64_t* d_bases, const ui
     KG_HIP(ctx, hipEventRecord(ctx->ev_prep, ctx->stream));
     KG_HIP(ctx, hipStreamWaitEvent(ctx->sort_stream, ctx->ev_prep, 0));
   }
-  // the bases: a registered array is resident already; otherwise ONE conversion for all groups, on a reduction queue (idle
-  // at this point) beside the scalar conversion
+  // the bases: a registered array is resident already, and an array the accumulation gathers as it lies needs no conversion
+  // (acc_abi_bases); otherwise ONE conversion for all groups, on a reduction queue (idle at this point) beside the scalar conversion
   bool resident = false;
   size_t off = 0;
   for (const auto& r : ctx->registered)
     if (covers(r, curve, d_bases, d_inf, n, &off)) { resident = true; break; }
   const bool f64 = resident_fmt64(n);
+  if (!resident && kg::acc_abi_bases(ctx, curve, d_bases, d_inf, n)) resident = true;      // gathered as the caller holds them: msm_run_multi_t applies the same rule to the job
   if (!resident) {
     const size_t bytes = n * (f64 ? (curve == KG_G2 ? 128 : 64) : (curve == KG_G2 ? 144 : 72));
     KG_TRY(ctx->ws_pb.ensure(DevMem{ctx, "resident-bases allocation"}, bytes, bytes / 8));

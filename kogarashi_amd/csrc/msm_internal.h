@@ -10,6 +10,9 @@ int pick_window(size_t n, int forced);
 // resident form of a base array of n points / of window tables: true = 64-byte points (see msm.hip BaseIO::load_point64)
 bool resident_fmt64(size_t n);
 bool table_fmt64();
+// an unregistered array the accumulation gathers as the caller holds it, without a conversion pass (KG_ACC_ABI_BASES; msm_bases.h
+// load_point_abi): base-field curves, no identity-flag array, where the conversion would take the 64-byte form
+bool acc_abi_bases(const kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t n);
 // bases: ABI affine (x | y) + flags -> resident form, on queue st (k_prep_bases)
 void prep_bases_enqueue(int curve, hipStream_t st, const uint64_t* d_bases, const uint8_t* d_inf, size_t n, uint32_t* out, bool fmt64);
 // window tables: next[i] = 2^c * prev[i], both resident (k_table_next)

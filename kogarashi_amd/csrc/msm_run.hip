@@ -14,6 +14,9 @@ void prep_bases_enqueue(int curve, hipStream_t st, const uint64_t* d_bases, cons
   else if (curve == KG_GRUMPKIN) launch_prep_bases<Fr>(st, d_bases, d_inf, n, out, fmt64);
   else launch_prep_bases<Fq2>(st, d_bases, d_inf, n, out, fmt64);
 }
+bool acc_abi_bases(const kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t n) {
+  return ctx->tune.acc_abi_bases != 0 && (curve == KG_G1 || curve == KG_GRUMPKIN) && !d_inf && resident_fmt64(n) && ((uintptr_t)d_bases & 15) == 0;
+}
 void table_next_enqueue(int curve, hipStream_t st, const uint32_t* prev, size_t n, int c, uint32_t* next, bool fmt64) {
   const dim3 grid((unsigned)((n + 63) / 64));
   if (curve == KG_G1) hipLaunchKernelGGL(k_table_next<Fq>, grid, dim3(64), 0, st, prev, n, c, next, fmt64 ? 1 : 0);
@@ -50,7 +53,7 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const MsmRunJob* jobs, int 
   Lay lay[MAX_FUSED];
   AccSets A;
   A.nsets = njobs;
-  for (int k = 0; k < MAX_FUSED; ++k) { A.pb[k] = nullptr; A.idx_off[k] = 0; A.partial[k] = nullptr; A.tab_n[k] = 0; A.fmt64[k] = 0; }
+  for (int k = 0; k < MAX_FUSED; ++k) { A.pb[k] = nullptr; A.idx_off[k] = 0; A.partial[k] = nullptr; A.tab_n[k] = 0; A.fmt[k] = BASES_72; }
   for (int k = 0; k < njobs; ++k) {
     const MsmRunJob& J = jobs[k];
     Lay& Y = lay[k];
@@ -58,7 +61,7 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const MsmRunJob* jobs, int 
     const uint32_t* reg_pb = nullptr;               // bases inside a registered array are already in packed internal form
     if (J.packed) {                                 // or the caller converted them (kg_msm: once for all window groups)
       if (S.merged_shift) return set_err(ctx, KG_ERR_BAD_ARG, "merged sort against caller-converted bases");
-      reg_pb = J.packed; A.fmt64[k] = J.packed64 ? 1 : 0; shared_pb = true;
+      reg_pb = J.packed; A.fmt[k] = J.packed64 ? BASES_64 : BASES_72; shared_pb = true;
     }
     for (const auto& r : ctx->registered) {
       if (reg_pb) break;
@@ -69,16 +72,23 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const MsmRunJob* jobs, int 
         if (!r.table || r.table_c != c || r.table_W != S.windows) continue;
         reg_pb = r.table.as<uint32_t>() + off * (r.table64 ? 2 * BaseIO<F>::PK : PW);
         A.tab_n[k] = (uint32_t)r.n;
-        A.fmt64[k] = r.table64 ? 1 : 0;
+        A.fmt[k] = r.table64 ? BASES_64 : BASES_72;
       } else {
         reg_pb = r.packed.as<uint32_t>() + off * (r.fmt64 ? 2 * BaseIO<F>::PK : PW);
-        A.fmt64[k] = r.fmt64 ? 1 : 0;
+        A.fmt[k] = r.fmt64 ? BASES_64 : BASES_72;
       }
       break;
     }
     if (S.merged_shift && !reg_pb) return set_err(ctx, KG_ERR_BAD_ARG, "merged sort against bases without a matching window table");
+    // An array nobody converted, of a base-field curve and without identity flags, is gathered where it lies (BASES_ABI): no
+    // conversion pass, no converted copy in the run space, nothing on the scalar queue and no event but the sort's in front of the accumulation.
+    // Its order against bases still in flight on the main queue is the accumulation queue's own: st is the main queue or follows it (above).
+    if (!reg_pb && BaseIO<F>::HAS_ABI && acc_abi_bases(ctx, Cfg::ID, J.d_bases, J.d_inf, J.nbases)) {
+      reg_pb = reinterpret_cast<const uint32_t*>(J.d_bases);
+      A.fmt[k] = BASES_ABI;
+    }
     const bool conv64 = !reg_pb && resident_fmt64(J.nbases);          // per-call conversion: the same rule as registration
-    if (conv64) A.fmt64[k] = 1;
+    if (conv64) A.fmt[k] = BASES_64;
     Y.o_pb = cv.take(reg_pb ? 256 : J.nbases * (conv64 ? 2 * BaseIO<F>::PK : PW) * 4);
     for (int i = 0; i < 2; ++i) {
       Y.o_lc[i] = cv.take(npts * 4); Y.o_lr[i] = cv.take(npts * 4); Y.o_lb[i] = cv.take((size_t)(W + 1) * 4);

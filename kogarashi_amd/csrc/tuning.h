@@ -23,6 +23,7 @@
   X(gather_fuse, "KG_GATHER_FUSE", 1, "0 = the bucket gather writes the dense bucket array instead of fusing the first halving level") \
   X(fmt64_min_log, "KG_FMT64_MIN_LOG", 0, "log2 of the array length from which resident bases take the 64-byte point form (30 = always the 72-byte limb form)") \
   X(table64, "KG_TABLE64", 1, "0 = window tables in the 72-byte limb form") \
+  X(acc_abi_bases, "KG_ACC_ABI_BASES", 1, "0 = an unregistered G1 / Grumpkin array without identity flags is converted to the resident form on every call instead of being gathered by the accumulation as the caller holds it") \
   X(pipe_accq, "KG_PIPE_ACCQ", 1, "2 = MSM tickets alternate between two accumulation queues (measured level; off)") \
   X(coop_tail, "KG_COOP_TAIL", 1, "0 = the last reduction of a blocking MSM runs the streamed tail kernel (96 VGPRs) instead of the lane-cooperative one") \
   X(small_max, "KG_SMALL_MAX", 32768, "longest MSM (pairs) that runs as the short-input kernel (msm_small.hip): 0 = never, at most 32768 (G2: 20480)") \
