@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .lib import KG_CHECK_CURVE, KG_CHECK_SUBGROUP, KG_FQ, KG_FR, KG_G1, KG_G2, KG_GRUMPKIN, Context, Groth16Crs
+from .lib import KG_CHECK_CURVE, KG_CHECK_SUBGROUP, KG_FQ, KG_FR, KG_G1, KG_G2, KG_GRUMPKIN, Context, Groth16Crs, KogarashiError
 
 _default_ctx = None
 CURVE_IDS = {"g1": KG_G1, "grumpkin": KG_GRUMPKIN, "gk": KG_GRUMPKIN, "g2": KG_G2}
@@ -319,6 +319,26 @@ class Prover:
         self.ctx.groth16_prove_batch(self.crs, da.ptr, db.ptr, dc.ptr, self.m, dx.ptr, self.l, dw.ptr if self.m_l_1 else 0, self.m_l_1,
                                      dr.ptr, ds.ptr, count, d_out.ptr, d_inf.ptr)
         return d_out.numpy(), d_inf.numpy()      # (kg_memcpy_d2h follows the stream)
+
+    def create_proofs_batch_from_witness(self, jobs):
+        """create_proofs_batch from witnesses alone: jobs are (x, w, r, s), the evaluation vectors of every proof are made on the device
+        from the attached constraint system (attach_constraint_system; kg_groth16_prove_r1cs_batch).  Returns the same (proofs, flags) of
+        shape (count, 32) and (count, 3); proof b equals create_proof_from_witness(*jobs[b]) bit for bit."""
+        if not hasattr(self, "_cs"):
+            raise KogarashiError("create_proofs_batch_from_witness needs attach_constraint_system first")
+        jobs = list(jobs)
+        count = len(jobs)
+        if count == 0:
+            return np.zeros((0, 32), dtype=np.uint64), np.zeros((0, 3), dtype=np.uint8)
+        pack = lambda k, n: np.ascontiguousarray(np.stack([np.asarray(j[k], dtype=np.uint64).reshape(-1, 4)[:n].reshape(n, 4) for j in jobs]))
+        up = lambda a: self.ctx.upload(a if a.size else np.zeros((1, 4), dtype=np.uint64))
+        dx, dw = up(pack(0, self.l)), up(pack(1, self.m_l_1))
+        dr, ds = up(pack(2, 1)), up(pack(3, 1))
+        ptrs = [tuple(d.ptr for d in trip) for trip in self._cs]
+        d_out, d_inf = self.ctx.empty((count, 32)), self.ctx.empty((count, 3), dtype=np.uint8)
+        self.ctx.groth16_prove_r1cs_batch(self.crs, ptrs[0], ptrs[1], ptrs[2], dx.ptr, self.l, dw.ptr if self.m_l_1 else 0, self.m_l_1,
+                                          dr.ptr, ds.ptr, count, d_out.ptr, d_inf.ptr)
+        return d_out.numpy(), d_inf.numpy()
 
 
 class ShardedProver:

@@ -427,6 +427,10 @@ struct MsmSorted {
 // vec.hip: CSR matrix-vector product on a given queue; ws: a region of kg_ctx::ws_vec that nothing else uses meanwhile
 int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
                       const uint64_t* z, uint64_t* out, const RowWs& ws);
+// ... against `count` vectors: vector b at element b * z_stride of z, its m row sums at element b * out_stride of out (kg_r1cs_prod_batch
+// after its argument checks; the work list is built once per call)
+int r1cs_prod_batch_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
+                            const uint64_t* z, size_t z_stride, size_t count, uint64_t* out, size_t out_stride, const RowWs& ws);
 // ntt.hip
 int ntt_prepare(kg_ctx* ctx, uint32_t log_n, int inverse);
 int ntt_enqueue(kg_ctx* ctx, hipStream_t st, uint64_t* tmp, uint64_t* d_data, uint32_t log_n, int inverse, int coset);

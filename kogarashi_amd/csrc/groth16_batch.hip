@@ -7,9 +7,12 @@
 // three kernels assemble the proofs (groth16_assemble.h): the G1 chains with one lane per (proof, chain), the G2 chain and B with one lane
 // per proof, and a finishing lane per proof for A and C.  Everything is enqueued on the context's stream; nothing crosses to the host and
 // no worker thread is involved.  The number of launches does not depend on the group's size.
+// kg_groth16_prove_r1cs_batch is the same from the witnesses alone: the constraint matrices take the place of the evaluation vectors, the
+// fill kernel zeroes the rows and three batched CSR products (vec.hip: r1cs_prod_batch_enqueue) write A z, B z, C z straight into them.
 #include "common.h"
 #include "groth16_qap.h"
 #include "groth16_batch.h"
+#include "r1cs_batch.h"
 #include "groth16_assemble.h"
 #include <climits>
 
@@ -21,12 +24,14 @@ constexpr int G16_NT = 64;                               // one wave per workgro
 
 // ---- fill: padded rows and z ------------------------------------------------------------------------------------------------------------
 struct G16FillArgs {
-  const uint64_t* src[3];                                // the three evaluation arrays, at the group's first proof
+  const uint64_t* src[3];                                // the three evaluation arrays, at the group's first proof (null in the R1CS form)
   const uint64_t *x, *w;
   size_t eval_stride, x_stride, w_stride, m, l, nz, n, g;
   uint64_t* dst;                                         // [3][g][n] then [g][nz]
 };
-// element e of the group's polynomial and z arrays <- the caller's strided arrays (zero beyond m); one 32-byte element per lane
+// element e of the group's polynomial and z arrays <- the caller's strided arrays (zero beyond m); one 32-byte element per lane.
+// EVALS = false (the R1CS form): there are no evaluation arrays, the rows are zeroed whole -- the batched products fill [0, m) next
+template <bool EVALS>
 __global__ void __launch_bounds__(256) k_g16_fill(G16FillArgs a) {
   KG_SERVICE_PRIO();
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -34,9 +39,11 @@ __global__ void __launch_bounds__(256) k_g16_fill(G16FillArgs a) {
   if (e >= rows + a.g * a.nz) return;
   uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (e < rows) {
-    const size_t row = e / a.n, i = e - row * a.n, vec = row / a.g, b = row - vec * a.g;
-    const uint64_t* s = vec == 0 ? a.src[0] : (vec == 1 ? a.src[1] : a.src[2]);
-    if (i < a.m) load_words(s, b * a.eval_stride + i, v);
+    if constexpr (EVALS) {
+      const size_t row = e / a.n, i = e - row * a.n, vec = row / a.g, b = row - vec * a.g;
+      const uint64_t* s = vec == 0 ? a.src[0] : (vec == 1 ? a.src[1] : a.src[2]);
+      if (i < a.m) load_words(s, b * a.eval_stride + i, v);
+    }
   } else {
     const size_t t = e - rows, b = t / a.nz, j = t - b * a.nz;
     if (j < a.l) load_words(a.x, b * a.x_stride + j, v);
@@ -185,6 +192,7 @@ struct G16BatchCall {
   size_t eval_stride, x_stride, w_stride;
   uint64_t* proofs;
   uint8_t* inf;
+  const kg_csr* mats[3];                                 // the R1CS form (kg_groth16_prove_r1cs_batch): a, b, c are null, the rows come from these
 };
 int g16_batch_group_run(kg_ctx* ctx, const G16BatchCall& q, size_t first, size_t g, char* ws, const Words8& zinv, const G16VkG1& vk1, const G16VkG2& vk2) {
   const kg_groth16_crs* crs = q.crs;
@@ -198,16 +206,26 @@ int g16_batch_group_run(kg_ctx* ctx, const G16BatchCall& q, size_t first, size_t
   uint8_t *f_a = (uint8_t*)(ws + L.flags), *f_b1 = f_a + g, *f_l = f_b1 + g, *f_h = f_l + g, *f_b2 = f_h + g;
   {
     G16FillArgs fa;
-    fa.src[0] = q.a + first * q.eval_stride * 4; fa.src[1] = q.b + first * q.eval_stride * 4; fa.src[2] = q.c + first * q.eval_stride * 4;
+    const bool evals = q.mats[0] == nullptr;
+    const uint64_t* src[3] = {q.a, q.b, q.c};
+    for (int v = 0; v < 3; ++v) fa.src[v] = evals ? src[v] + first * q.eval_stride * 4 : nullptr;
     fa.x = q.x + first * q.x_stride * 4;
     fa.w = q.w ? q.w + first * q.w_stride * 4 : nullptr;
     fa.eval_stride = q.eval_stride; fa.x_stride = q.x_stride; fa.w_stride = q.w_stride;
     fa.m = m; fa.l = l; fa.nz = nz; fa.n = n; fa.g = g; fa.dst = A;
     const size_t elems = g * (3 * n + nz);
     PhaseScope ph(ctx, "g16_batch_fill", st);
-    hipLaunchKernelGGL(k_g16_fill, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, fa);
+    hipLaunchKernelGGL(evals ? k_g16_fill<true> : k_g16_fill<false>, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, fa);
     ph.end();
     KG_HIP(ctx, hipGetLastError());
+    if (!evals) {                                          // cs.evaluate() of the whole group: three batched products straight into the rows
+      PhaseScope pe(ctx, "g16_batch_evaluate", st);
+      uint64_t* rows[3] = {A, B, C};
+      for (int v = 0; v < 3; ++v)
+        KG_TRY(r1cs_prod_batch_enqueue(ctx, st, KG_FR, q.mats[v]->d_row_ptr, q.mats[v]->d_col, q.mats[v]->d_val, m, Z, nz, g, rows[v], n,
+                                       RowWs(ctx->ws_vec.get(), m, v)));
+      pe.end();
+    }
   }
   KG_TRY(kg_ntt_bn254_fr_batch(ctx, A, k, 3 * g, n, 1, 0));                 // idft, coset_dft of all rows (prover.rs:36-41)
   KG_TRY(kg_ntt_bn254_fr_batch(ctx, A, k, 3 * g, n, 0, 1));
@@ -241,6 +259,28 @@ int g16_batch_group_run(kg_ctx* ctx, const G16BatchCall& q, size_t first, size_t
   return KG_OK;
 }
 
+// both entries behind their argument checks; q.mats decides the form
+int g16_batch_run(kg_ctx* ctx, const G16BatchCall& q, size_t count) {
+  const kg_groth16_crs* crs = q.crs;
+  const size_t m = crs->m, l = crs->l, m_l_1 = crs->m_l_1;
+  if (crs->delta_g1_inf || crs->delta_g2_inf) return set_err(ctx, KG_ERR_CRS, "delta is the identity");      // prover.rs:67-69
+  size_t per = 0;
+  const size_t groups = g16_batch_plan(m, l, m_l_1, count, ctx->tune.g16_batch_mb, [count](int curve, size_t len) { return len_ok(curve, len, count); }, &per);
+  if (groups == 0) return set_err(ctx, KG_ERR_UNSUPPORTED, "an MSM length of the circuit is outside the batched short MSM's (kg_commit_batch_plan)");
+  KG_HIP(ctx, hipSetDevice(ctx->device));
+  KG_TRY(ctx->ws_g16_batch.ensure(DevMem{ctx, "batched prover scratch"}, per * g16_batch_proof_bytes(m, l, m_l_1)));
+  if (q.mats[0]) KG_TRY(ctx->ws_vec.ensure(DevMem{ctx, "workspace allocation"}, RowWs::bytes(m)));       // a work list per matrix, every group's
+  const Words8 zinv = qap_zinv(g16_batch_log(m));
+  G16VkG1 vk1;
+  G16VkG2 vk2;
+  vk_words(crs->alpha_g1, 8, vk1.alpha); vk_words(crs->beta_g1, 8, vk1.beta1); vk_words(crs->delta_g1, 8, vk1.delta1);
+  vk_words(crs->beta_g2, 16, vk2.beta2); vk_words(crs->delta_g2, 16, vk2.delta2);
+  for (size_t gi = 0; gi < groups; ++gi) {                  // one after another on the stream: every group uses the same scratch
+    const G16BatchGroup grp = g16_batch_group(per, count, gi);
+    KG_TRY(g16_batch_group_run(ctx, q, grp.first, grp.count, ctx->ws_g16_batch.as<char>(), zinv, vk1, vk2));
+  }
+  return KG_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -255,27 +295,26 @@ int kg_groth16_prove_batch(kg_ctx* ctx, const kg_groth16_crs* crs, const uint64_
                            const uint64_t* d_s, size_t count, uint64_t* d_proofs, uint8_t* d_proof_inf) {
   return kg::kg_guarded(ctx, [&]() -> int {
   if (!ctx || !crs) return KG_ERR_BAD_ARG;
-  const size_t m = crs->m, l = crs->l, m_l_1 = crs->m_l_1;
-  if (!g16_batch_args_ok(ctx, crs, m, l, m_l_1, d_a_eval, d_b_eval, d_c_eval, eval_stride, d_x, x_stride, d_w, w_stride, d_r, d_s, count, d_proofs, d_proof_inf))
+  if (!g16_batch_args_ok(ctx, crs, crs->m, crs->l, crs->m_l_1, d_a_eval, d_b_eval, d_c_eval, eval_stride, d_x, x_stride, d_w, w_stride, d_r, d_s, count, d_proofs,
+                         d_proof_inf))
     return KG_ERR_BAD_ARG;
   if (count == 0) return KG_OK;
-  if (crs->delta_g1_inf || crs->delta_g2_inf) return set_err(ctx, KG_ERR_CRS, "delta is the identity");      // prover.rs:67-69
-  size_t per = 0;
-  const size_t groups = g16_batch_plan(m, l, m_l_1, count, ctx->tune.g16_batch_mb, [count](int curve, size_t len) { return len_ok(curve, len, count); }, &per);
-  if (groups == 0) return set_err(ctx, KG_ERR_UNSUPPORTED, "an MSM length of the circuit is outside the batched short MSM's (kg_commit_batch_plan)");
-  KG_HIP(ctx, hipSetDevice(ctx->device));
-  KG_TRY(ctx->ws_g16_batch.ensure(DevMem{ctx, "batched prover scratch"}, per * g16_batch_proof_bytes(m, l, m_l_1)));
-  const Words8 zinv = qap_zinv(g16_batch_log(m));
-  G16VkG1 vk1;
-  G16VkG2 vk2;
-  vk_words(crs->alpha_g1, 8, vk1.alpha); vk_words(crs->beta_g1, 8, vk1.beta1); vk_words(crs->delta_g1, 8, vk1.delta1);
-  vk_words(crs->beta_g2, 16, vk2.beta2); vk_words(crs->delta_g2, 16, vk2.delta2);
-  const G16BatchCall q{crs, d_a_eval, d_b_eval, d_c_eval, d_x, d_w, d_r, d_s, eval_stride, x_stride, w_stride, d_proofs, d_proof_inf};
-  for (size_t gi = 0; gi < groups; ++gi) {                  // one after another on the stream: every group uses the same scratch
-    const G16BatchGroup grp = g16_batch_group(per, count, gi);
-    KG_TRY(g16_batch_group_run(ctx, q, grp.first, grp.count, ctx->ws_g16_batch.as<char>(), zinv, vk1, vk2));
-  }
-  return KG_OK;
+  return g16_batch_run(ctx, G16BatchCall{crs, d_a_eval, d_b_eval, d_c_eval, d_x, d_w, d_r, d_s, eval_stride, x_stride, w_stride, d_proofs, d_proof_inf,
+                                         {nullptr, nullptr, nullptr}}, count);
+  });
+}
+
+// The R1CS form: the constraint matrices instead of the three evaluation arrays.  The fill kernel zeroes the rows and builds z, three
+// batched products (vec.hip) write A z, B z, C z of the whole group straight into the rows; from the transforms on it is the code above.
+int kg_groth16_prove_r1cs_batch(kg_ctx* ctx, const kg_groth16_crs* crs, const kg_csr* a, const kg_csr* b, const kg_csr* c, const uint64_t* d_x,
+                                size_t x_stride, const uint64_t* d_w, size_t w_stride, const uint64_t* d_r, const uint64_t* d_s, size_t count,
+                                uint64_t* d_proofs, uint8_t* d_proof_inf) {
+  return kg::kg_guarded(ctx, [&]() -> int {
+  if (!ctx || !crs) return KG_ERR_BAD_ARG;
+  if (!g16_r1cs_batch_args_ok(ctx, crs, crs->m, crs->l, crs->m_l_1, a, b, c, d_x, x_stride, d_w, w_stride, d_r, d_s, count, d_proofs, d_proof_inf))
+    return KG_ERR_BAD_ARG;
+  if (count == 0) return KG_OK;
+  return g16_batch_run(ctx, G16BatchCall{crs, nullptr, nullptr, nullptr, d_x, d_w, d_r, d_s, crs->m, x_stride, w_stride, d_proofs, d_proof_inf, {a, b, c}}, count);
   });
 }
 

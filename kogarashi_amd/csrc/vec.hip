@@ -6,6 +6,7 @@
 #include "common.h"
 #include "vecops.h"
 #include "host_fp.h"
+#include "r1cs_batch.h"
 
 using namespace kg;
 
@@ -178,11 +179,11 @@ __global__ void __launch_bounds__(256) k_rows_wave(Op op, uint32_t* __restrict__
 // row holds an entry per constraint -- 2^18 entries on 64 lanes took 4.8 ms of a 29 ms setup.  Rows of 49 .. 4096 entries (a range check's bit
 // sum: 254) keep a wave each: a circuit may hold tens of thousands of them, and 1024 waves take them in parallel.
 constexpr int LONG_NT = 1024;
+// (the body of both huge-row kernels: the single product's and the batch's, which hands in its vector's z and out)
 template <class P>
-__global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
-                                                            const uint64_t* __restrict__ val, const uint64_t* __restrict__ z, uint64_t* __restrict__ out,
-                                                            const uint32_t* __restrict__ long_rows, const uint32_t* __restrict__ long_count, size_t m) {
-  KG_SERVICE_PRIO();
+__device__ __forceinline__ void rows_huge(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col, const uint64_t* __restrict__ val,
+                                          const uint64_t* __restrict__ z, uint64_t* __restrict__ out, const uint32_t* __restrict__ long_rows,
+                                          const uint32_t* __restrict__ long_count, size_t m) {
   __shared__ uint32_t part[LONG_NT / 64][9];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t total = long_count[1];
@@ -217,6 +218,22 @@ __global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge(const uint64_t* __re
     __syncthreads();
   }
 }
+template <class P>
+__global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
+                                                            const uint64_t* __restrict__ val, const uint64_t* __restrict__ z, uint64_t* __restrict__ out,
+                                                            const uint32_t* __restrict__ long_rows, const uint32_t* __restrict__ long_count, size_t m) {
+  KG_SERVICE_PRIO();
+  rows_huge<P>(row_ptr, col, val, z, out, long_rows, long_count, m);
+}
+// the batch's: a workgroup per (list entry, vector), the vector is the block's y index (strides in elements)
+template <class P>
+__global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge_batch(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
+                                                                  const uint64_t* __restrict__ val, const uint64_t* __restrict__ z, size_t z_stride,
+                                                                  uint64_t* __restrict__ out, size_t out_stride, const uint32_t* __restrict__ long_rows,
+                                                                  const uint32_t* __restrict__ long_count, size_t m) {
+  KG_SERVICE_PRIO();
+  rows_huge<P>(row_ptr, col, val, z + (size_t)blockIdx.y * z_stride * 4, out + (size_t)blockIdx.y * out_stride * 4, long_rows, long_count, m);
+}
 
 // out = M z  (zkstd/src/matrix/row.rs:43-51, matrix.rs:36-48): long rows to the list's front, huge rows to its back
 template <class P>
@@ -234,6 +251,23 @@ struct ProdOp {
       store_words(out, row, wo);
     }
     return false;
+  }
+};
+// out_b = M z_b for the vectors of one chunk of a batch (kg_r1cs_prod_batch): the walker's kernels as they are over a grid whose y index is
+// the vector -- a lane per (short row, vector), a wave per (list entry, vector).  A row's class depends on the matrix alone, so the work
+// list is built once: by the y = 0 blocks of the launch that `lists` (the batch's first chunk).  Every other lane that meets a long row
+// leaves it to the list's launches; trip counts stay wave-uniform, the list and its counters being the same for every y.
+template <class P>
+struct ProdBatchOp {
+  static constexpr bool REPORTS = false;
+  CsrView M; const uint64_t* z; uint64_t* out; size_t z_stride, out_stride; bool lists;      // strides in elements
+  __device__ __forceinline__ ProdOp<P> vec() const { return {M, z + (size_t)blockIdx.y * z_stride * 4, out + (size_t)blockIdx.y * out_stride * 4}; }
+  __device__ __forceinline__ int klass(size_t row) const { return lists && blockIdx.y == 0 ? vec().klass(row) : 0; }
+  template <int G>
+  __device__ __forceinline__ bool row(size_t row, int lane) const {
+    const ProdOp<P> v = vec();
+    if (G == 1 && v.klass(row) != 0) return false;          // a list's row: not this lane's
+    return v.template row<G>(row, lane);
   }
 };
 
@@ -491,6 +525,28 @@ int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }
+// one matrix against `count` vectors (strides in elements, r1cs_batch.h): a memset and three launches per chunk of 65535 vectors, whatever
+// count is; the first chunk's first launch builds the work list, every later launch reads it
+int r1cs_prod_batch_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
+                            const uint64_t* z, size_t z_stride, size_t count, uint64_t* out, size_t out_stride, const RowWs& ws) {
+  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, st));
+  by_field(field, [&](auto p) {
+    using P = decltype(p);
+    for (size_t i = 0; i < r1cs_batch_chunks(count); ++i) {
+      const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
+      const uint64_t* zc = z + ch.first * z_stride * 4;
+      uint64_t* oc = out + ch.first * out_stride * 4;
+      const ProdBatchOp<P> op{{row_ptr, col, val}, zc, oc, z_stride, out_stride, i == 0};
+      const unsigned y = (unsigned)ch.count;
+      hipLaunchKernelGGL(k_rows_lane<ProdBatchOp<P>>, dim3(grid256(m).x, y), dim3(256), 0, st, op, m, ws);
+      hipLaunchKernelGGL(k_rows_wave<ProdBatchOp<P>>, dim3(r1cs_batch_grid_x(256, ch.count), y), dim3(256), 0, st, op, ws.summary, ws.list, ws.count);
+      hipLaunchKernelGGL(k_r1cs_rows_huge_batch<P>, dim3(r1cs_batch_grid_x(64, ch.count), y), dim3(LONG_NT), 0, st, row_ptr, col, val, zc, z_stride, oc,
+                         out_stride, ws.list, ws.count, m);
+    }
+  });
+  KG_HIP(c, hipGetLastError());
+  return KG_OK;
+}
 }  // namespace kg
 
 extern "C" {
@@ -503,6 +559,15 @@ int kg_r1cs_prod(kg_ctx* c, int field, const uint64_t* row_ptr, const uint64_t* 
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
   KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
   return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, out, RowWs(c->ws_vec.get(), m));
+}
+
+int kg_r1cs_prod_batch(kg_ctx* c, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z,
+                       size_t z_stride, size_t count, uint64_t* out, size_t out_stride) {
+  if (!r1cs_batch_args_ok(c, field, row_ptr, col, val, m, z, z_stride, count, out, out_stride)) return KG_ERR_BAD_ARG;
+  if (r1cs_batch_empty(m, count)) return KG_OK;
+  KG_HIP(c, hipSetDevice(c->device));
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  return kg::r1cs_prod_batch_enqueue(c, c->stream, field, row_ptr, col, val, m, z, z_stride, count, out, out_stride, RowWs(c->ws_vec.get(), m));
 }
 
 int kg_r1cs_evaluate(kg_ctx* c, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z, uint64_t* out) {

@@ -35,6 +35,7 @@ EXPORTS = [
     "kg_ntt_bn254_fr_batch", "kg_fr_divide_by_z_on_coset_batch", "kg_ntt_batch_plan",
     "kg_commit_batch", "kg_commit_batch_plan",
     "kg_groth16_prove_batch", "kg_groth16_prove_batch_plan",
+    "kg_r1cs_prod_batch", "kg_groth16_prove_r1cs_batch",
 ]
 
 
@@ -114,6 +115,12 @@ def load():
                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         _lib.kg_groth16_prove_batch_plan.restype = C.c_int
         _lib.kg_groth16_prove_batch_plan.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]
+        _lib.kg_r1cs_prod_batch.restype = C.c_int
+        _lib.kg_r1cs_prod_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                            C.c_void_p, C.c_size_t]
+        _lib.kg_groth16_prove_r1cs_batch.restype = C.c_int
+        _lib.kg_groth16_prove_r1cs_batch.argtypes = [C.c_void_p, C.POINTER(Groth16Crs), C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -439,6 +446,12 @@ class Context:
     def r1cs_prod(self, field: int, row_ptr: int, col: int, val: int, m: int, z: int, out: int):
         self._chk(self._lib.kg_r1cs_prod(self._h, field, _vp(row_ptr), _vp(col), _vp(val), C.c_size_t(m), _vp(z), _vp(out)), "kg_r1cs_prod")
 
+    def r1cs_prod_batch(self, field: int, row_ptr: int, col: int, val: int, m: int, z: int, z_stride: int, count: int, out: int, out_stride: int):
+        """kg_r1cs_prod_batch: one CSR matrix against count vectors; vector b at element b * z_stride of z, its m row sums at element
+        b * out_stride of out (strides in elements).  Enqueued on the context's stream: valid in stream order or after sync()."""
+        self._chk(self._lib.kg_r1cs_prod_batch(self._h, int(field), _vp(row_ptr), _vp(col), _vp(val), C.c_size_t(m), _vp(z), C.c_size_t(z_stride),
+                                               C.c_size_t(count), _vp(out), C.c_size_t(out_stride)), "kg_r1cs_prod_batch")
+
     def nova_cross_term(self, field: int, a, b, c, m: int, z1: int, z2: int, u1: np.ndarray, u2: np.ndarray, out: int):
         """kg_nova_cross_term; a, b, c: (row_ptr, col, val) device pointers"""
         mk = lambda t: Csr(_vp(t[0]), _vp(t[1]), _vp(t[2]))
@@ -489,6 +502,18 @@ class Context:
         if rc == -6:
             raise ProverSubVersionCrsAttack("delta is the identity")
         self._chk(rc, "kg_groth16_prove_batch")
+
+    def groth16_prove_r1cs_batch(self, crs: "Groth16Crs", a, b, c, x: int, x_stride: int, w: int, w_stride: int, r: int, s: int, count: int, proofs: int,
+                                 proof_inf: int):
+        """kg_groth16_prove_r1cs_batch: groth16_prove_batch with the constraint matrices a, b, c = (row_ptr, col, val) device pointers (CSR over
+        x || w) in the place of the evaluation arrays.  Enqueued on the context's stream."""
+        mk = lambda t: Csr(_vp(t[0]), _vp(t[1]), _vp(t[2]))
+        ca, cb, cc = mk(a), mk(b), mk(c)
+        rc = self._lib.kg_groth16_prove_r1cs_batch(self._h, C.byref(crs), C.byref(ca), C.byref(cb), C.byref(cc), _vp(x), C.c_size_t(x_stride), _vp(w),
+                                                   C.c_size_t(w_stride), _vp(r), _vp(s), C.c_size_t(count), _vp(proofs), _vp(proof_inf))
+        if rc == -6:
+            raise ProverSubVersionCrsAttack("delta is the identity")
+        self._chk(rc, "kg_groth16_prove_r1cs_batch")
 
     def groth16_prove_begin(self, crs: "Groth16Crs", a_eval: int, b_eval: int, c_eval: int, x: int, w: int, r: np.ndarray, s: np.ndarray, ticket: int):
         """kg_groth16_prove_begin: enqueue a proof (ticket 0 or 1); crs and the device inputs stay alive until the end."""
