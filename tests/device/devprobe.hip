@@ -9,6 +9,7 @@
 #include <vector>
 #include "../host/arith_cases.h"
 #include "../../kogarashi_amd/csrc/msm_small_kernels.h"
+#include "../../kogarashi_amd/csrc/msm_reduce_kernels.h"
 
 using namespace kgcase;
 
@@ -144,6 +145,78 @@ int run_coop(const uint32_t* items, const uint32_t* params, uint32_t* o, uint8_t
   return (int)B.st;
 }
 
+// ---- the lane-pair Fq2 (fp2s.h): element i lives on lanes 2i (c0) and 2i + 1 (c1); NT is even, so a pair never straddles a workgroup ----------
+using S2 = kg::Fp2S<Fq>;
+enum Fp2sOp { S_MUL = 0, S_SQR, S_MUL2SUB, S_IS_ZERO, S_IS_ZERO_2P, S_ONE };
+// a, b, c, d: 18 raw limbs per element (c0 | c1), taken as they are; out: 18 words per element, each lane writes its own nine (a verdict: the
+// first of them, so that the two lanes' verdicts can be compared)
+__global__ void __launch_bounds__(NT) k_fp2s_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n) {
+  const size_t i = ((size_t)blockIdx.x * NT + threadIdx.x) >> 1;
+  if (i >= n) return;                                    // whole pairs: both lanes of a pair leave together
+  const size_t o = 18 * i + 9 * (size_t)S2::half();
+  const S2 x{Raw<Fq>::limbs(a + o, nullptr)}, y{Raw<Fq>::limbs(b + o, nullptr)}, z{Raw<Fq>::limbs(c + o, nullptr)}, w{Raw<Fq>::limbs(d + o, nullptr)};
+  S2 r = S2::zero();
+  bool flag = false, limbs_out = true;
+  switch (op) {
+    case S_MUL: r = mul(x, y); break;
+    case S_SQR: r = sqr(x); break;
+    case S_MUL2SUB: r = mul2sub(x, y, z, w); break;
+    case S_IS_ZERO: flag = is_zero(x); limbs_out = false; break;
+    case S_IS_ZERO_2P: flag = is_zero_2p(x); limbs_out = false; break;
+    case S_ONE: r = S2::one(); break;
+    default: break;
+  }
+  if (limbs_out) { for (int k = 0; k < 9; ++k) out[o + k] = r.v.l[k]; }
+  else out[o] = flag ? 1u : 0u;
+}
+
+// The stream formulas of curve.h on XYZZ<Fp2S<Fq>> through the reduction's own accessors (msm_reduce_kernels.h).  A point is 72 raw limbs:
+// array of structures = the one-lane PointAoS<Fp2<Fq>> words (x.c0 x.c1 y.c0 ... zzz.c1), structure of arrays = word k of point i at [k * n + i].
+// route 0: AosSrc, AosSrc -> AosDst (k_sum_tasks); 1: AosSrc, AosSrc -> SoaDst (k_gather_halve, k_gather_sum); 2: SoaSrc, SoaSrc -> SoaDst (k_halve).
+// op 0 add_xyzz_stream, 1 double_xyzz_stream (of p), 2 copy_xyzz_stream (of p).  inplace: p is copied into the output slot first and the formula
+// then runs with that slot as its first operand AND its destination, as the running sums of k_gather_sum / k_sum_tasks do.
+// flags[i]: bit 0 the pair is active (an idle pair returns at once and writes nothing), bit 1 / bit 2 p / q is an EMPTY array-of-structures slot
+// (AosSrc valid = false: the identity without a read).
+enum { FL_ACTIVE = 1, FL_P_EMPTY = 2, FL_Q_EMPTY = 4 };
+template <class A, class B, class Cur, class D>
+__device__ __forceinline__ void fp2s_curve_case(int op, int inplace, const A& p, const B& q, const Cur& cur, D& dst) {
+  if (op == 2) { kg::copy_xyzz_stream<S2>(p, dst); return; }
+  if (!inplace) {
+    if (op == 0) kg::add_xyzz_stream<S2>(p, q, dst); else kg::double_xyzz_stream<S2>(p, dst);
+    return;
+  }
+  kg::copy_xyzz_stream<S2>(p, dst);
+  KG_STREAM_FENCE();
+  if (op == 0) kg::add_xyzz_stream<S2>(cur, q, dst); else kg::double_xyzz_stream<S2>(cur, dst);
+}
+template <int ROUTE>
+__global__ void __launch_bounds__(NT) k_fp2s_curve(int op, int inplace, const uint32_t* p, const uint32_t* q, const uint8_t* flags, uint32_t* out, uint32_t n) {
+  using namespace kg::msm;
+  const uint32_t i = (blockIdx.x * (uint32_t)NT + threadIdx.x) >> 1;
+  if (i >= n) return;
+  const uint32_t f = flags[i];
+  if (!(f & FL_ACTIVE)) return;
+  constexpr uint32_t NWB = (uint32_t)kg::PointIO<S2>::NW * 4u;     // bytes per array-of-structures point
+  const BufRsrc rp = soa_rsrc(p), rq = soa_rsrc(q), ro = soa_rsrc(out);
+  const uint32_t s4 = n * 4u;
+  if constexpr (ROUTE == 2) {
+    const SoaSrc<S2> sp{rp, s4, i * 4u}, sq{rq, s4, i * 4u}, cur{ro, s4, i * 4u};
+    SoaDst<S2> dst{ro, s4, i * 4u};
+    fp2s_curve_case(op, inplace, sp, sq, cur, dst);
+  } else {
+    const AosSrc<S2> sp{rp, i * NWB, !(f & FL_P_EMPTY)}, sq{rq, i * NWB, !(f & FL_Q_EMPTY)};
+    if constexpr (ROUTE == 0) {
+      const AosSrc<S2> cur{ro, i * NWB, true};
+      AosDst<S2> dst{ro, i * NWB};
+      fp2s_curve_case(op, inplace, sp, sq, cur, dst);
+    } else {
+      const SoaSrc<S2> cur{ro, s4, i * 4u};
+      SoaDst<S2> dst{ro, s4, i * 4u};
+      fp2s_curve_case(op, inplace, sp, sq, cur, dst);
+    }
+  }
+}
+
 template <class F>
 int run_raw(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, const uint32_t* k, uint32_t* out, size_t n) {
   Bufs B;
@@ -202,6 +275,36 @@ int dp_raw2_ops(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c,
   uint32_t* dout = B.out<uint32_t>(RAW_OUT * n);
   if (B.ok()) { k_raw2<Fq><<<blocks(n), NT>>>(op, da, db, dc, dd, dout, n); B.launched(); }
   B.back(out, dout, RAW_OUT * n);
+  return (int)B.st;
+}
+// Fp2S<Fq> on raw limbs (k_fp2s_raw): the operand arrays of dp_raw2_ops
+int dp_fp2s_raw_ops(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* out, size_t n) {
+  if (n == 0) return 0;
+  if (op < S_MUL || op > S_ONE) return -1;
+  Bufs B;
+  const uint32_t *da = B.in(a, 18 * n), *db = B.in(b, 18 * n), *dc = B.in(c, 18 * n), *dd = B.in(d, 18 * n);
+  uint32_t* dout = B.out<uint32_t>(RAW_OUT * n);
+  if (B.ok()) { k_fp2s_raw<<<blocks(2 * n), NT>>>(op, da, db, dc, dd, dout, n); B.launched(); }
+  B.back(out, dout, RAW_OUT * n);
+  return (int)B.st;
+}
+// the stream formulas on XYZZ<Fp2S<Fq>> (k_fp2s_curve); p, q, out: 72 n words each in the layout of the route; out goes in as the caller filled it
+// (an idle pair leaves its slot as it was) and comes back
+int dp_fp2s_curve_ops(int op, int route, int inplace, const uint32_t* p, const uint32_t* q, const uint8_t* flags, uint32_t* out, size_t n) {
+  if (n == 0) return 0;
+  if (op < 0 || op > 2 || route < 0 || route > 2 || n > ((size_t)1 << 20)) return -1;      // (72 words x 2^20 points: byte offsets stay below 2^32)
+  Bufs B;
+  const uint32_t *dp = B.in(p, 72 * n), *dq = B.in(q, 72 * n);
+  const uint8_t* df = B.in(flags, n);
+  uint32_t* dout = B.alloc<uint32_t>(72 * n);
+  if (B.ok()) B.st = hipMemcpy(dout, out, 72 * n * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (B.ok()) {
+    if (route == 0) k_fp2s_curve<0><<<blocks(2 * n), NT>>>(op, inplace, dp, dq, df, dout, (uint32_t)n);
+    else if (route == 1) k_fp2s_curve<1><<<blocks(2 * n), NT>>>(op, inplace, dp, dq, df, dout, (uint32_t)n);
+    else k_fp2s_curve<2><<<blocks(2 * n), NT>>>(op, inplace, dp, dq, df, dout, (uint32_t)n);
+    B.launched();
+  }
+  B.back(out, dout, 72 * n);
   return (int)B.st;
 }
 // field: 0 Fr, 1 Fq, 2 Fq2; the arguments of ht_field_ops (ABI-form elements)

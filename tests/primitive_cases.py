@@ -893,7 +893,382 @@ def check_glv_digits(ks, dig, W, c, lam, n):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
+# Fp2S<Fq>, the lane-pair Fq2 of csrc/fp2s.h (device only): element i on lanes 2i (c0) and 2i + 1 (c1)
+#
+# operand table of dp_fp2s_raw_ops (Batch2 rows, 18 raw limbs per operand):
+#   mul         raw2_batches()[0] (canonical specials and the a0 b0 = a1 b1 (+-1) relations, non-canonical, K 9) + the half classes below
+#   sqr         raw2_batches()[1]: canonical, K 6, non-canonical (5.4) -- fp2s.h asks for normalised limbs and K <= 6, the SAME class fp29.h
+#               states for the one-lane square, so nothing of that table had to be left out; + the half classes below
+#   mul2sub     raw2_batches()[2] + rows of the half classes
+#   is_zero     every pairing of {0, p, 2p, 3p, 167p} and non-multiples on the two halves (K 168)
+#   is_zero_2p  every pairing of {0, p} and values of [0, 2p) that differ from 0 / p in one bit of one limb
+#   one         Fp2S::one() on every lane pair of two waves
+# half classes: exactly one half zero, both zero, one half equal to p or to 2p (zero as a value, not as limbs)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+FP2S_OPS = {"mul": 0, "sqr": 1, "mul2sub": 2, "is_zero": 3, "is_zero_2p": 4, "one": 5}
+Q = P.Q_MOD
+R261_INV_Q = pow(R261, -1, Q)
+
+
+def fp2s_half_elements():
+    rnd = random.Random(2929)
+    nz = [1, Q - 1, (Q + 1) // 2] + [rnd.randrange(1, Q) for _ in range(3)]
+    el = [(0, 0)] + [(0, x) for x in nz] + [(x, 0) for x in nz]
+    el += [(Q, x) for x in nz[:3]] + [(x, Q) for x in nz[:3]] + [(2 * Q, x) for x in nz[:3]] + [(x, 2 * Q) for x in nz[:3]]
+    el += [(Q, 0), (0, Q), (Q, Q), (2 * Q, Q), (Q, 2 * Q), (2 * Q, 2 * Q), (2 * Q, 0), (0, 2 * Q)]
+    return el
+
+
+def fp2s_batches():
+    rnd = random.Random(2930)
+    B2 = raw2_batches()
+    H = fp2s_half_elements()
+    full = [(rnd.randrange(Q), rnd.randrange(Q)) for _ in range(6)]
+    others = H + full
+    hp = [(H[i], others[(i * 7 + s) % len(others)]) for s in (0, 1, 5) for i in range(len(H))] + [(f, h) for f in full[:2] for h in H]
+    hq = [(H[i], others[(i * 3 + 1) % len(others)], others[(i * 5 + 2) % len(others)], H[(i + 4) % len(H)]) for i in range(len(H))]
+    hq += [(a, b, a, b) for a, b in hp[:12]] + [(a, b, b, a) for a, b in hp[:12]]
+    mult, nonm = [0, Q, 2 * Q, 3 * Q, 167 * Q], [1, Q - 1, Q + 1, 2 * Q - 1, 2 * Q + 1, 167 * Q + 1, rnd.randrange(1, Q)]
+    z_all = [((a, b),) for a in mult + nonm for b in mult + nonm]
+    pl = limbs(Q)
+    flip = [val(pl[:i] + [pl[i] ^ (1 << b)] + pl[i + 1:]) for i in range(9) for b in (0, 28 if i < 8 else 21)]
+    flip = [x for x in flip if x < 2 * Q] + [1 << (29 * i) for i in range(9)]
+    z2, n2 = [0, Q], [1, Q - 1, Q + 1, 2 * Q - 1] + flip
+    z2_all = [((a, b),) for a in z2 for b in z2] * 4 + [((a, b),) for a in z2 for b in n2] + [((b, a),) for a in z2 for b in n2]
+    z2_all += [((n2[i], n2[(i + 3) % len(n2)]),) for i in range(len(n2))]
+    return {
+        "mul": B2[0] + [Batch2("one half zero / p / 2p", hp, ("5.4", "5.4"))],
+        "sqr": B2[1] + [Batch2("one half zero / p / 2p (K <= 6, normalised: the class fp2s.h states)", [(h,) for h in H], ("5.4",))],
+        "mul2sub": B2[2] + [Batch2("one half zero / p / 2p", hq, ("5.4",) * 4)],
+        "is_zero": [Batch2("multiples of p and their neighbours on either half", z_all, (168,))],
+        "is_zero_2p": [Batch2("[0, 2p): 0, p and one-bit neighbours on either half", z2_all, (2,))],
+        "one": [Batch2("no operand", [((0, 0),)] * 70, (1,))],
+    }
+
+
+def check_fp2s(prim, batch, i, o):
+    """the lane pair's 18 output words against Python integers: the congruence of both halves, normalised limbs, and the bound fp29.h documents
+    for the primitive that PRODUCES each half (mul2pm: [0, 2p); mul: (Ka Kb / 169 + 1) p; vred: 1.06 p).  Verdicts: both lanes, equal and right."""
+    r, K = batch.rows[i], batch.K
+    o = [int(v) for v in o]
+    if prim in ("is_zero", "is_zero_2p"):
+        ((a0, a1),) = r
+        want = 1 if (a0 % Q == 0 and a1 % Q == 0) else 0
+        assert o[0] == o[9], "the two lanes of the pair disagree"
+        assert o[0] == want and not any(o[1:9]) and not any(o[10:]), "verdict"
+        return
+    if prim == "one":
+        assert o[:9] == limbs(R261 % Q) and not any(o[9:]), "one() is (1, 0) in the internal form"
+        return
+    c0, c1 = val(o[:9]), val(o[9:18])
+    assert _normalised(o[:9]) and _normalised(o[9:18]), "limbs not below 2^29"
+    if prim == "mul":
+        (a0, a1), (b0, b1) = r
+        assert (c0 * R261 - (a0 * b0 - a1 * b1)) % Q == 0, "congruence of c0"
+        assert (c1 * R261 - (a0 * b1 + a1 * b0)) % Q == 0, "congruence of c1"
+        assert c0 < 2 * Q and c1 < 2 * Q, "mul2pm: [0, 2p)"
+    elif prim == "sqr":
+        ((a0, a1),) = r
+        assert (c0 * R261 - (a0 * a0 - a1 * a1)) % Q == 0, "congruence of c0"
+        assert (c1 * R261 - 2 * a0 * a1) % Q == 0, "congruence of c1"
+        assert c0 * 169 < (2 * K[0] * (K[0] + 8) + 169) * Q and c1 * 169 < (2 * K[0] * K[0] + 169) * Q, "bounds"
+    elif prim == "mul2sub":
+        a, b, c, d = (P.Fq2(x[0], x[1]) for x in r)
+        want = a * b - c * d
+        assert (c0 * R261 - want.a) % Q == 0, "congruence of c0"
+        assert (c1 * R261 - want.b) % Q == 0, "congruence of c1"
+        assert c0 * 100 < 106 * Q and c1 * 100 < 106 * Q, "value above 1.06 p"
+    else:
+        raise KeyError(prim)
+
+
+def fp2s_expected(prim, batch, i):
+    """one output the checker accepts (canonical halves): what the self-test mutates"""
+    r = batch.rows[i]
+    if prim in ("is_zero", "is_zero_2p"):
+        f = 1 if (r[0][0] % Q == 0 and r[0][1] % Q == 0) else 0
+        return [f] + [0] * 8 + [f] + [0] * 8
+    if prim == "one":
+        return limbs(R261 % Q) + [0] * 9
+    e = [P.Fq2(x[0], x[1]) for x in r]
+    v = {"mul": lambda: e[0] * e[1], "sqr": lambda: e[0] * e[0], "mul2sub": lambda: e[0] * e[1] - e[2] * e[3]}[prim]()
+    return limbs(v.a * R261_INV_Q % Q) + limbs(v.b * R261_INV_Q % Q)
+
+
+def check_fp2s_batch(prim, b, out):
+    for i in range(len(b)):
+        try:
+            check_fp2s(prim, b, i, out[i])
+        except AssertionError as e:
+            raise AssertionError(f"Fp2S {prim} class '{b.name}' row {i}: {e}; operands {b.rows[i]}, out {[hex(int(v)) for v in out[i]]}") from None
+
+
+def dev_fp2s(D, prim, b):
+    out = np.full((len(b), RAW_OUT), 0xA5A5A5A5, dtype=np.uint32)
+    st = D.dp_fp2s_raw_ops(FP2S_OPS[prim], _p(b.arr[0]), _p(b.arr[1]), _p(b.arr[2]), _p(b.arr[3]), _p(out), C.c_size_t(len(b)))
+    assert st == 0, f"HIP status {st}"
+    return out
+
+
+def canonical_halves(out):
+    return [(val(r[:9]) % Q, val(r[9:18]) % Q) for r in out]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the stream formulas on XYZZ<Fp2S<Fq>> through the reduction's accessors (dp_fp2s_curve_ops).  A point is 72 raw limbs in the order of the
+# one-lane PointAoS<Fp2<Fq>>: x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1; a limb vector holds value * 2^261 mod p.  The reference is the
+# XYZZ formulas themselves (add-2008-s, dbl-2008-s-1) over pyoracle.Fq2 integers: every coordinate must agree, not only the affine point.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+S_ROUTES = {"AosSrc -> AosDst": 0, "AosSrc -> SoaDst": 1, "SoaSrc -> SoaDst": 2}
+S_ACTIVE, S_P_EMPTY, S_Q_EMPTY = 1, 2, 4
+S_PAIRS = 32                                                                # lane pairs of a wave = of a workgroup of the probe
+S_KINDS = ("ordinary", "doubling", "cancelling", "O+A", "A+O", "O+O", "P=(0,x)", "P=(x,0)", "P=0 R=(0,x)", "P=0 R=(x,0)", "ZZ half zero")
+F2_ZERO, F2_ONE = P.Fq2(0, 0), P.Fq2(1, 0)
+O4 = (F2_ZERO,) * 4
+
+
+def f2_raw(x):
+    return limbs(x.a * R261 % Q) + limbs(x.b * R261 % Q)
+
+
+def pt_raw(pt):
+    return [w for x in pt for w in f2_raw(x)]
+
+
+def raw_f2(w):
+    return P.Fq2(val(w[:9]) * R261_INV_Q, val(w[9:18]) * R261_INV_Q)
+
+
+def raw_pt(w):
+    return tuple(raw_f2(w[18 * k:18 * k + 18]) for k in range(4))
+
+
+def xyzz_dbl_ref(p):
+    x, y, zz, zzz = p
+    u = y * 2
+    v = u * u
+    w = u * v
+    s = x * v
+    m = x * x * 3
+    x3 = m * m - s * 2
+    return (x3, m * (s - x3) - w * y, v * zz, w * zzz)
+
+
+def xyzz_add_ref(p, q):
+    """(result, branch): 'copy q', 'copy p', 'doubling', 'identity' or 'generic'"""
+    if p[2].is_zero():
+        return q, "copy q"
+    if q[2].is_zero():
+        return p, "copy p"
+    u1, u2, s1, s2 = p[0] * q[2], q[0] * p[2], p[1] * q[3], q[1] * p[3]
+    pp_, r = u2 - u1, s2 - s1
+    pp = pp_ * pp_
+    if pp.is_zero():
+        return (xyzz_dbl_ref(p), "doubling") if r.is_zero() else (O4, "identity")
+    ppp = pp_ * pp
+    qq = u1 * pp
+    x3 = r * r - ppp - qq * 2
+    return (x3, r * (qq - x3) - s1 * ppp, p[2] * q[2] * pp, p[3] * q[3] * ppp), "generic"
+
+
+def _half(x):
+    return None if x.is_zero() else ("(0,x)" if x.a == 0 else ("(x,0)" if x.b == 0 else None))
+
+
+def s_kind(p, q):
+    """the kind of an addition from the operands' VALUES"""
+    zp, zq = p[2].is_zero(), q[2].is_zero()
+    if zp or zq:
+        return "O+O" if zp and zq else ("O+A" if zp else "A+O")
+    pp_, r = q[0] * p[2] - p[0] * q[2], q[1] * p[3] - p[1] * q[3]
+    if pp_.is_zero():
+        if r.is_zero():
+            return "doubling"
+        return "P=0 R=" + _half(r) if _half(r) else "cancelling"
+    if _half(pp_):
+        return "P=" + _half(pp_)
+    if _half(p[2]) or _half(q[2]):
+        return "ZZ half zero"
+    return "ordinary"
+
+
+def _abi_f2(w):
+    return P.Fq2(P.from_mont(I(w[:4]), Q), P.from_mont(I(w[4:8]), Q))
+
+
+def _patch_p(raw, coord, half):
+    """the same value with a zero half written as the limbs of p (the _2p form of zero)"""
+    o = 18 * coord + 9 * half
+    assert not any(raw[o:o + 9])
+    return raw[:o] + limbs(Q) + raw[o + 9:]
+
+
+def fp2s_curve_cases():
+    """[(name, p raw, q raw, flags)] of the additions, before they are dealt into waves: the group cases of curve_case_arrays(P.G2, ...) and the
+    half-zero operand sets (field values, not curve points)"""
+    rnd = random.Random(7117)
+    rf = lambda: P.Fq2(rnd.randrange(1, Q), rnd.randrange(1, Q))
+    cases = []
+    ps, qs, _, names = curve_case_arrays(P.G2, "add_xyzz_stream")
+    for name, pr, qr in zip(names, ps, qs):
+        pt, qt = (tuple(_abi_f2(r[8 * k:8 * k + 8]) for k in range(4)) for r in (pr, qr))
+        cases.append((name, pt_raw(pt), pt_raw(qt), 0))
+    A = curve_points(P.G2)[0]
+    a1 = (A[0], A[1], F2_ONE, F2_ONE)
+    cases += [("empty+A", [0xDEAD] * 72, pt_raw(a1), S_P_EMPTY), ("A+empty", pt_raw(a1), [0xBEEF] * 72, S_Q_EMPTY),
+              ("empty+empty", [0xDEAD] * 72, [0xBEEF] * 72, S_P_EMPTY | S_Q_EMPTY)]
+    for rep in range(2):
+        for d in (P.Fq2(0, rnd.randrange(1, Q)), P.Fq2(rnd.randrange(1, Q), 0), P.Fq2(0, 1), P.Fq2(Q - 1, 0)):
+            x1, y1, y2 = rf(), rf(), rf()
+            cases.append(("P half zero, z = 1", pt_raw((x1, y1, F2_ONE, F2_ONE)), pt_raw((x1 + d, y2, F2_ONE, F2_ONE)), 0))
+            zz1, zzz1, zz2, zzz2 = rf(), rf(), rf(), rf()
+            cases.append(("P half zero, any z", pt_raw((x1, y1, zz1, zzz1)), pt_raw(((x1 * zz2 + d) * zz1.inv(), y2, zz2, zzz2)), 0))
+            # the full-zero difference: R = d (half zero) must give the identity; R = 0 under unrelated denominators is a doubling
+            cases.append(("P = 0, R half zero, z = 1", pt_raw((x1, y1, F2_ONE, F2_ONE)), pt_raw((x1, y1 + d, F2_ONE, F2_ONE)), 0))
+            cases.append(("P = 0, R half zero, any z", pt_raw((x1, y1, zz1, zzz1)),
+                          pt_raw((x1 * zz2 * zz1.inv(), (y1 * zzz2 + d) * zzz1.inv(), zz2, zzz2)), 0))
+            cases.append(("P = 0, R = 0, any z", pt_raw((x1, y1, zz1, zzz1)), pt_raw((x1 * zz2 * zz1.inv(), y1 * zzz2 * zzz1.inv(), zz2, zzz2)), 0))
+        for hz in (P.Fq2(0, rnd.randrange(1, Q)), P.Fq2(rnd.randrange(1, Q), 0)):
+            half = 0 if hz.a == 0 else 1
+            full = (rf(), rf(), rf(), rf())
+            one_side = (rf(), rf(), hz, rf())
+            cases.append(("ZZ1 half zero", pt_raw(one_side), pt_raw(full), 0))
+            cases.append(("ZZ2 half zero", pt_raw(full), pt_raw(one_side), 0))
+            cases.append(("ZZ1, ZZ2 half zero", pt_raw(one_side), pt_raw((rf(), rf(), hz, rf())), 0))
+            cases.append(("ZZ1 half p", _patch_p(pt_raw(one_side), 2, half), pt_raw(full), 0))
+            cases.append(("ZZ2 half p", pt_raw(full), _patch_p(pt_raw(one_side), 2, half), 0))
+    # zero as limbs of p on one or both halves of ZZ: the identity
+    ident = pt_raw((rf(), rf(), F2_ZERO, rf()))
+    full = pt_raw((rf(), rf(), rf(), rf()))
+    for halves in ((0,), (1,), (0, 1)):
+        z = ident
+        for h in halves:
+            z = _patch_p(z, 2, h)
+        cases += [("ZZ1 = 0 as p", z, full, 0), ("ZZ2 = 0 as p", full, z, 0), ("ZZ1 = ZZ2 = 0 as p", z, ident, 0)]
+    return cases
+
+
+def fp2s_curve_waves():
+    """The additions dealt into waves of 32 lane pairs: full waves in which every kind of S_KINDS is present, one wave whose LAST pair alone is
+    active, and a partial last workgroup.  Returns p, q (n, 72) uint32, flags (n,) uint8, kinds [n] (None: idle), names [n]."""
+    cases = fp2s_curve_cases()
+    by = {k: [] for k in S_KINDS}
+    for c in cases:
+        by[s_kind(*_case_values(c))].append(c)
+    assert all(by[k] for k in S_KINDS), {k: len(v) for k, v in by.items()}
+    order, used = [], {k: 0 for k in S_KINDS}
+    tail = 11                                                               # pairs of the partial last workgroup
+    while not all(used[k] >= len(by[k]) for k in S_KINDS) or len(order) % S_PAIRS:
+        k = S_KINDS[len(order) % len(S_KINDS)]
+        order.append(by[k][used[k] % len(by[k])])
+        used[k] += 1
+    lone = [by["P=(0,x)"][0]] * S_PAIRS
+    rows = [(c, S_ACTIVE) for c in order] + [(c, S_ACTIVE if i == S_PAIRS - 1 else 0) for i, c in enumerate(lone)]
+    rows += [(by[S_KINDS[i % len(S_KINDS)]][-1], S_ACTIVE) for i in range(tail)]
+    p = np.array([c[1] for c, _ in rows], dtype=np.uint32)
+    q = np.array([c[2] for c, _ in rows], dtype=np.uint32)
+    flags = np.array([c[3] | a for c, a in rows], dtype=np.uint8)
+    kinds = [s_kind(*_case_values(c)) if a else None for c, a in rows]
+    return p, q, flags, kinds, [c[0] for c, _ in rows]
+
+
+def fp2s_double_waves():
+    """the first operands of fp2s_curve_waves for double_xyzz_stream (never the identity: its callers filter it), every fourth one replaced by a
+    point with one half of X or of Y zero"""
+    rnd = random.Random(7118)
+    rf = lambda: P.Fq2(rnd.randrange(1, Q), rnd.randrange(1, Q))
+    p, q, flags0, _, _ = fp2s_curve_waves()
+    p, flags = p.copy(), flags0 & S_ACTIVE
+    extra = [pt_raw((rf(), P.Fq2(0, rnd.randrange(1, Q)), rf(), rf())), pt_raw((rf(), P.Fq2(rnd.randrange(1, Q), 0), rf(), rf())),
+             pt_raw((P.Fq2(0, rnd.randrange(1, Q)), rf(), rf(), rf())), pt_raw((P.Fq2(rnd.randrange(1, Q), 0), rf(), rf(), F2_ONE))]
+    for i in range(len(p)):
+        if i % 4 == 3 or flags0[i] & S_P_EMPTY or raw_pt(p[i])[2].is_zero():
+            p[i] = extra[(i // 4) % 4]
+    return p, q, flags
+
+
+def _case_values(c):
+    _, pr, qr, fl = c
+    return (O4 if fl & S_P_EMPTY else raw_pt(pr)), (O4 if fl & S_Q_EMPTY else raw_pt(qr))
+
+
+def assert_fp2s_waves_are_mixed(kinds, flags):
+    """every full wave but the lone one holds every kind at once; the lone wave's last pair is its only active one; the last workgroup is partial"""
+    n = len(kinds)
+    nfull = n // S_PAIRS
+    assert n % S_PAIRS != 0 and nfull >= 3
+    lone = [w for w in range(nfull) if sum(1 for k in kinds[w * S_PAIRS:(w + 1) * S_PAIRS] if k) == 1]
+    assert len(lone) == 1 and kinds[lone[0] * S_PAIRS + S_PAIRS - 1] is not None
+    for w in range(nfull):
+        if w not in lone:
+            kd = kinds[w * S_PAIRS:(w + 1) * S_PAIRS]
+            assert all(k in kd for k in S_KINDS), (w, kd)
+    assert all(k for k in kinds[nfull * S_PAIRS:])
+    assert all(bool(f & S_ACTIVE) == (k is not None) for f, k in zip(flags, kinds))
+
+
+FILL = 0xA5A5A5A5
+
+
+def fp2s_curve_expected(op, pr, qr, fl):
+    """(kind of check, value): ('bits', 72 words) where the formula copies or writes zeros, ('value', 4 Fq2, computed X/Y?) where it computes"""
+    p = O4 if fl & S_P_EMPTY else raw_pt(pr)
+    q = O4 if fl & S_Q_EMPTY else raw_pt(qr)
+    img = lambda raw, empty: [0] * 72 if empty else [int(v) for v in raw]
+    if op == "copy":
+        return "bits", img(pr, fl & S_P_EMPTY)
+    if op == "double":
+        return "value", xyzz_dbl_ref(p)
+    res, branch = xyzz_add_ref(p, q)
+    if branch == "copy q":
+        return "bits", img(qr, fl & S_Q_EMPTY)
+    if branch == "copy p":
+        return "bits", img(pr, fl & S_P_EMPTY)
+    if branch == "identity":
+        return "bits", [0] * 72                                             # curve.h: every path that produces the identity writes zeros
+    return "value", res
+
+
+def check_fp2s_curve(op, pr, qr, fl, out):
+    """one active pair's 72 output words"""
+    how, want = fp2s_curve_expected(op, pr, qr, fl)
+    out = [int(v) for v in out]
+    if how == "bits":
+        assert out == want, "a copied operand / the identity, bit for bit"
+        return
+    assert all(v <= M29 for v in out), "limbs not below 2^29"
+    got = raw_pt(out)
+    for k, nm in enumerate(("X", "Y", "ZZ", "ZZZ")):
+        assert got[k] == want[k], f"{nm} differs from the formula over Fq2 integers"
+        for h in (0, 1):
+            v = val(out[18 * k + 9 * h:18 * k + 9 * h + 9])
+            assert (v * 100 < 106 * Q) if k < 2 else (v < 2 * Q), f"{nm} half {h}: above the bound curve.h keeps for a stored coordinate"
+
+
+def fp2s_curve_good_output(op, pr, qr, fl):
+    """an output the checker accepts: what the self-test mutates"""
+    how, want = fp2s_curve_expected(op, pr, qr, fl)
+    return list(want) if how == "bits" else pt_raw(want)
+
+
+def dev_fp2s_curve(D, op, route, inplace, p, q, flags):
+    """runs the probe; SoA operands are transposed here.  Returns out (n, 72) in the array-of-structures order whatever the route"""
+    n = p.shape[0]
+    soa_in, soa_out = route == 2, route in (1, 2)
+    if soa_in:                                                              # a structure-of-arrays source has no empty flag: the identity is zeros
+        p, q = p.copy(), q.copy()
+        p[(flags & S_P_EMPTY) != 0] = 0
+        q[(flags & S_Q_EMPTY) != 0] = 0
+    pa = np.ascontiguousarray(p.T) if soa_in else p
+    qa = np.ascontiguousarray(q.T) if soa_in else q
+    out = np.full((72, n) if soa_out else (n, 72), FILL, dtype=np.uint32)
+    st = D.dp_fp2s_curve_ops({"add": 0, "double": 1, "copy": 2}[op], route, int(inplace), _p(pa), _p(qa), flags.ctypes.data_as(U8P), _p(out), C.c_size_t(n))
+    assert st == 0, f"HIP status {st}"
+    return np.ascontiguousarray(out.T) if soa_out else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
 # the probe library
 # ---------------------------------------------------------------------------------------------------------------------------------------
 DEV_EXPORTS = ["dp_raw_ops", "dp_raw2_ops", "dp_field_ops", "dp_curve_ops", "dp_coop_ops", "dp_small_digits", "dp_glv_decompose", "dp_glv_digits",
-               "dp_endo"]
+               "dp_endo", "dp_fp2s_raw_ops", "dp_fp2s_curve_ops"]

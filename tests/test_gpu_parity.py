@@ -236,9 +236,11 @@ def test_msm_skewed_scalars(ctx, oracle, c):
 
 
 def test_msm_degenerate_inputs_hit_the_exceptional_branches(ctx, oracle):
-    """One base repeated with one scalar: every addition after the first meets an equal point (doubling branch of
-    add_mixed / add_xyzz, weierstrass.rs:75-81,114-120) and every bucket list is maximally skewed; alternating P, -P
-    cancels to the identity through the inverse-point branch."""
+    """One base repeated with one scalar: every addition after the first meets an equal point (the doubling branches,
+    weierstrass.rs:75-81,114-120) and every bucket list is maximally skewed; alternating P, -P cancels to the identity
+    through the inverse-point branch.  6000 pairs are below the short kernel's limit (32768), so by default this runs
+    k_msm_small and its cooperative formulas (coop_add.h), not add_mixed / add_xyzz of the long pipeline it was written
+    for: tests/test_gpu_long_edges.py puts the same inputs through the long pipeline (kg_msm_set_small(0))."""
     O = oracle
     n = 6000
     P = O.gen_bases(0, SEED + 95, 0, 1)[0]
