@@ -493,6 +493,45 @@ int kg_nova_cross_term(kg_ctx* ctx, int field, const kg_csr* a, const kg_csr* b,
 enum { KG_ROW_UNSAT = 1 };   /* per-row status */
 int kg_r1cs_check(kg_ctx* ctx, int field, const kg_csr* a, const kg_csr* b, const kg_csr* c, size_t m, const uint64_t* d_z,
                   const uint64_t* h_u, const uint64_t* d_e, uint8_t* d_status, size_t* out_bad, size_t* out_first_bad);
+/* kg_r1cs_check for count vectors against ONE shape in one call, results left on the device: what a host runs in front of
+ * kg_groth16_prove_r1cs_batch, or around a batch of Nova folds.  Vector b is read at d_z + b * z_stride * 4 words, E_b at
+ * d_e + b * e_stride * 4 words (strides in ELEMENTS), u_b = d_u[b] (4 words, the ABI's Montgomery form like every element).  Row i of
+ * vector b is bad iff (A z_b)_i (B z_b)_i - u_b (C z_b)_i - E_b,i != 0 (mod p).
+ * d_u: DEVICE, count elements; NULL: u = 1 for every vector.  d_e: DEVICE; NULL: E = 0, nothing is read.  d_status: DEVICE, may be NULL;
+ * row i's byte (0 or KG_ROW_UNSAT) goes to d_status[b * status_stride + i], status_stride in BYTES; the bytes between two vectors' rows are
+ * neither read nor written.  d_summary: DEVICE, 2 * count 32-bit words: d_summary[2 b] = the number of bad rows of vector b,
+ * d_summary[2 b + 1] = its smallest bad row, m when there is none -- for every b exactly what the single call returns and writes for
+ * (z_b, u_b, E_b).
+ * The batch family's stream rule: ENQUEUED on the context's stream, does not block, reads nothing back, starts no worker thread; results
+ * are valid in stream order or after kg_ctx_sync.  One initialising launch per call (the pairs to (0, m), the work list's counters), then
+ * two launches per chunk of 65535 vectors whatever count is: a lane per (short row, vector), a wave per (listed row, vector).  A row is
+ * long when it has more than 48 entries in any of the three matrices -- the shape alone decides, so the work list is built once, by the
+ * first chunk's first launch.  Each wave folds its bad rows into its vector's pair with at most one atomic add and one atomic min.
+ * PRECONDITIONS as for kg_r1cs_check and kg_r1cs_prod_batch (rows ascend, columns inside each vector, canonical values, strides trusted).
+ * count == 0: KG_OK, nothing enqueued.  m == 0 with count > 0: every pair becomes (0, 0).  KG_ERR_BAD_ARG, decided before anything is
+ * dereferenced or enqueued: a null ctx; an unknown field; m >= 2^32; a null d_summary with count > 0; and for count > 0 and m > 0 a null
+ * kg_csr or member array, a null d_z, e_stride < m with d_e given, status_stride < m with d_status given, a count * stride * 32 beyond
+ * size_t.
+ * Measured (chain circuit over Fr, every witness valid, no status array; profiles/r1cs_check_batch_timing.txt: this call + sync against
+ * count blocking single calls on pre-built z vectors, medians of alternating rounds): 256 vectors of 2^4 / 2^10 / 2046 / 2^14 constraints
+ * 0.044 / 0.075 / 0.098 / 0.287 ms against 8.82 / 9.50 / 9.70 / 10.19 ms; 16 vectors 0.043 / 0.044 / 0.052 / 0.043 against 0.56 / 0.60 /
+ * 0.61 / 0.67; 4 vectors 0.044 / 0.045 / 0.045 / 0.031 against 0.145 / 0.159 / 0.156 / 0.166 (interquartile ranges 1 .. 33 us for the
+ * batch, 4 .. 940 us for the loop).  No cell of that table loses to the loop; the floor of a call is ~0.04 ms (three launches and a sync).
+ * In front of the batched proving call on the same x / w the split form adds +0.025 / -0.007 / +0.015 ms to 25.0 / 56.9 / 75.0 ms at 256 proofs
+ * and between -0.42 and +0.31 ms at 4 and 16 proofs, every one of them INSIDE the rounds' spread (0.06 .. 1.5 ms): not measurable. */
+int kg_r1cs_check_batch(kg_ctx* ctx, int field, const kg_csr* a, const kg_csr* b, const kg_csr* c, size_t m, const uint64_t* d_z,
+                        size_t z_stride, size_t count, const uint64_t* d_u, const uint64_t* d_e, size_t e_stride, uint8_t* d_status,
+                        size_t status_stride, uint32_t* d_summary);
+/* The same check on the batch prover's own arrays, read in place: R1cs::is_sat (zkstd/src/r1cs.rs:62-77) over Fr with u = 1 and E = 0 for
+ * the witnesses z_b = x_b || w_b -- column j reads x_b[j] when j < l and w_b[j - l] otherwise.  d_x, x_stride, d_w, w_stride are laid out
+ * as kg_groth16_prove_r1cs_batch reads them, so one upload serves the check and the proving call behind it on the same stream.  No z is
+ * assembled: no scratch per witness, no copy; the split costs one compare and two selects per matrix entry.  It needs no CRS and is not
+ * bound to the batched MSM's 2048 pairs: any m below 2^32.  a, b, c: CSR with m rows over l + m_l_1 columns.
+ * d_status, status_stride, d_summary, the stream rule, count == 0 and m == 0: as above.  KG_ERR_BAD_ARG additionally for l < 1,
+ * x_stride < l, w_stride < m_l_1 (even for an empty call), a null d_x, a null d_w unless m_l_1 == 0. */
+int kg_groth16_witness_check_batch(kg_ctx* ctx, const kg_csr* a, const kg_csr* b, const kg_csr* c, size_t m, size_t l, size_t m_l_1,
+                                   const uint64_t* d_x, size_t x_stride, const uint64_t* d_w, size_t w_stride, size_t count,
+                                   uint8_t* d_status, size_t status_stride, uint32_t* d_summary);
 /* create_proof with cs.evaluate() (zkstd/src/r1cs.rs:137-142, prover.rs:33) on the device as well: the constraint matrices
  * a, b, c (CSR over z = x || w, m = crs->m rows; resident, uploaded once per circuit) take the place of the three
  * evaluation vectors -- each transform chain starts with its matrix-vector product.  Otherwise as kg_groth16_prove_bn254 /
@@ -510,7 +549,8 @@ int kg_groth16_prove_r1cs_begin(kg_ctx* ctx, const kg_groth16_crs* crs, const kg
  * outside the batched short MSM's, KG_ERR_CRS for a delta flag and KG_ERR_BAD_ARG -- all decided before anything is enqueued -- and
  * count == 0.  Additionally KG_ERR_BAD_ARG for a null kg_csr or a null member array (count > 0).
  * Proof b is bit-identical to kg_groth16_prove_r1cs_bn254 on (x_b, w_b, r_b, s_b), and to kg_groth16_prove_batch fed with
- * kg_r1cs_evaluate's outputs.  An unsatisfied witness yields a well-formed proof no verifier accepts (kg_r1cs_check is the test).
+ * kg_r1cs_evaluate's outputs.  An unsatisfied witness yields a well-formed proof no verifier accepts
+ * (kg_groth16_witness_check_batch on the same d_x / d_w, enqueued in front of this call, is the test; kg_r1cs_check one vector at a time).
  * Inside a launch group the fill kernel builds z = x || w in the scratch and zeroes the padded rows, then three kg_r1cs_prod_batch
  * launch sets (one per matrix; z_stride = l + m_l_1, out_stride = n) write A z, B z, C z of the whole group straight into the rows the
  * transforms run over: no staging array, no copy, and the launches per group still do not depend on its size (twelve enqueues more than

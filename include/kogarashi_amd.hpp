@@ -499,6 +499,41 @@ class R1csShape {
     if (e.size() != m_) throw std::invalid_argument("R1csShape: E has one element per constraint");
     return check(z, &u, &e, status);
   }
+  // is_sat_relaxed for several (z, u, E) against this shape in one kg_r1cs_check_batch: zs holds the vectors one after another (each
+  // zs.size() / us.size() elements), es the error vectors (m() elements each; empty: E = 0 for all), us one u per vector.
+  std::vector<Sat> is_sat_relaxed_batch(const std::vector<Fe>& zs, const std::vector<Fe>& us, const std::vector<Fe>& es) const {
+    const size_t count = us.size();
+    if (count == 0) return {};
+    if (zs.size() % count != 0 || (!es.empty() && es.size() != count * m_)) throw std::invalid_argument("R1csShape: one z, one u and one E per vector");
+    const size_t nz = zs.size() / count;
+    if (m_ && nz <= max_col_) throw std::out_of_range("R1csShape: z is shorter than the largest column index");
+    DeviceBuffer dz(c_, zs.data(), zs.size() * 32), du(c_, us.data(), count * 32), dsum(c_, count * 8);
+    std::unique_ptr<DeviceBuffer> de;
+    if (!es.empty()) de.reset(new DeviceBuffer(c_, es.data(), es.size() * 32));
+    c_.check(kg_r1cs_check_batch(c_.raw(), field_, &csr_[0], &csr_[1], &csr_[2], m_, dz.as<uint64_t>(), nz, count, du.as<uint64_t>(),
+                                 de ? de->as<uint64_t>() : nullptr, m_, nullptr, 0, dsum.as<uint32_t>()), "kg_r1cs_check_batch");
+    std::vector<uint32_t> h(2 * count);
+    dsum.download(h.data());
+    std::vector<Sat> r(count);
+    for (size_t b = 0; b < count; ++b) r[b] = Sat{h[2 * b], h[2 * b + 1]};
+    return r;
+  }
+  // R1cs::is_sat for several witnesses x_b || w_b of a Groth16 circuit with l instance wires (xs: l elements per witness, ws: the rest), read
+  // in place through kg_groth16_witness_check_batch -- the arrays kg_groth16_prove_r1cs_batch takes.  Fr only.
+  std::vector<Sat> is_sat_witness_batch(const std::vector<Fe>& xs, const std::vector<Fe>& ws, size_t l, size_t count) const {
+    if (count == 0) return {};
+    if (l == 0 || xs.size() != count * l || ws.size() % count != 0) throw std::invalid_argument("R1csShape: l instance wires and one w per witness");
+    const size_t m_l_1 = ws.size() / count;
+    if (m_ && l + m_l_1 <= max_col_) throw std::out_of_range("R1csShape: x || w is shorter than the largest column index");
+    DeviceBuffer dx(c_, xs.data(), xs.size() * 32), dw(c_, ws.data(), ws.size() * 32), dsum(c_, count * 8);
+    c_.check(kg_groth16_witness_check_batch(c_.raw(), &csr_[0], &csr_[1], &csr_[2], m_, l, m_l_1, dx.as<uint64_t>(), l, m_l_1 ? dw.as<uint64_t>() : nullptr, m_l_1,
+                                            count, nullptr, 0, dsum.as<uint32_t>()), "kg_groth16_witness_check_batch");
+    std::vector<uint32_t> h(2 * count);
+    dsum.download(h.data());
+    std::vector<Sat> r(count);
+    for (size_t b = 0; b < count; ++b) r[b] = Sat{h[2 * b], h[2 * b + 1]};
+    return r;
+  }
 
  private:
   Sat check(const std::vector<Fe>& z, const Fe* u, const std::vector<Fe>* e, std::vector<uint8_t>* status) const {

@@ -320,25 +320,54 @@ class Prover:
                                      dr.ptr, ds.ptr, count, d_out.ptr, d_inf.ptr)
         return d_out.numpy(), d_inf.numpy()      # (kg_memcpy_d2h follows the stream)
 
-    def create_proofs_batch_from_witness(self, jobs):
+    def _upload_witnesses(self, jobs):
+        """the first two members of every job, (x, w), as the packed device arrays the batch entries read (strides l and m_l_1)"""
+        pack = lambda k, n: np.ascontiguousarray(np.stack([np.asarray(j[k], dtype=np.uint64).reshape(-1, 4)[:n].reshape(n, 4) for j in jobs]))
+        up = lambda a: self.ctx.upload(a if a.size else np.zeros((1, 4), dtype=np.uint64))
+        return up(pack(0, self.l)), up(pack(1, self.m_l_1))
+
+    def _check_uploaded(self, dx, dw, count):
+        ptrs = [tuple(d.ptr for d in trip) for trip in self._cs]
+        return self.ctx.groth16_witness_check_batch(ptrs[0], ptrs[1], ptrs[2], self.m, self.l, self.m_l_1, dx.ptr, self.l,
+                                                    dw.ptr if self.m_l_1 else 0, self.m_l_1, count)
+
+    def check_witnesses(self, jobs) -> np.ndarray:
+        """check_witness for a list of jobs whose first two members are (x, w), in ONE call (kg_groth16_witness_check_batch): x and w are
+        uploaded as the batch prover takes them and read in place.  Returns an array (count, 2) of (number of violated constraints, index of
+        the first or m) per witness."""
+        if not hasattr(self, "_cs"):
+            raise KogarashiError("check_witnesses needs attach_constraint_system first")
+        jobs = list(jobs)
+        if not jobs:
+            return np.zeros((0, 2), dtype=np.uint32)
+        dx, dw = self._upload_witnesses(jobs)
+        return self._check_uploaded(dx, dw, len(jobs)).numpy()
+
+    def create_proofs_batch_from_witness(self, jobs, check=False):
         """create_proofs_batch from witnesses alone: jobs are (x, w, r, s), the evaluation vectors of every proof are made on the device
         from the attached constraint system (attach_constraint_system; kg_groth16_prove_r1cs_batch).  Returns the same (proofs, flags) of
-        shape (count, 32) and (count, 3); proof b equals create_proof_from_witness(*jobs[b]) bit for bit."""
+        shape (count, 32) and (count, 3); proof b equals create_proof_from_witness(*jobs[b]) bit for bit.
+        check=True enqueues kg_groth16_witness_check_batch on the uploaded x and w in front of the proving call and returns
+        (proofs, flags, summary), summary as check_witnesses returns it: proofs and flags are the same bits, a witness with summary[b, 0] != 0
+        has a proof no verifier accepts."""
         if not hasattr(self, "_cs"):
             raise KogarashiError("create_proofs_batch_from_witness needs attach_constraint_system first")
         jobs = list(jobs)
         count = len(jobs)
         if count == 0:
-            return np.zeros((0, 32), dtype=np.uint64), np.zeros((0, 3), dtype=np.uint8)
+            empty = (np.zeros((0, 32), dtype=np.uint64), np.zeros((0, 3), dtype=np.uint8))
+            return empty + (np.zeros((0, 2), dtype=np.uint32),) if check else empty
         pack = lambda k, n: np.ascontiguousarray(np.stack([np.asarray(j[k], dtype=np.uint64).reshape(-1, 4)[:n].reshape(n, 4) for j in jobs]))
         up = lambda a: self.ctx.upload(a if a.size else np.zeros((1, 4), dtype=np.uint64))
-        dx, dw = up(pack(0, self.l)), up(pack(1, self.m_l_1))
+        dx, dw = self._upload_witnesses(jobs)
         dr, ds = up(pack(2, 1)), up(pack(3, 1))
         ptrs = [tuple(d.ptr for d in trip) for trip in self._cs]
         d_out, d_inf = self.ctx.empty((count, 32)), self.ctx.empty((count, 3), dtype=np.uint8)
+        d_sum = self._check_uploaded(dx, dw, count) if check else None
         self.ctx.groth16_prove_r1cs_batch(self.crs, ptrs[0], ptrs[1], ptrs[2], dx.ptr, self.l, dw.ptr if self.m_l_1 else 0, self.m_l_1,
                                           dr.ptr, ds.ptr, count, d_out.ptr, d_inf.ptr)
-        return d_out.numpy(), d_inf.numpy()
+        out = (d_out.numpy(), d_inf.numpy())
+        return out + (d_sum.numpy(),) if check else out
 
 
 class ShardedProver:
@@ -532,6 +561,23 @@ class NovaProver:
             de = e if hasattr(e, "ptr") else self.ctx.upload(np.ascontiguousarray(e, dtype=np.uint64).reshape(-1, 4))
         ptrs = [tuple(d.ptr for d in trip) for trip in self._dev]
         return self.ctx.r1cs_check(self.field, ptrs[0], ptrs[1], ptrs[2], self.m, z.ptr, u, de.ptr if de is not None else 0)
+
+    def check_batch(self, pairs) -> np.ndarray:
+        """check() for a list of (u, x, w, e) against the shape in ONE call (kg_r1cs_check_batch): the z vectors (u | x | w), the u and the E
+        are uploaded as packed arrays.  e: (m, 4) host array or None (E = 0; when every e is None nothing is read).  Returns an array
+        (count, 2) of (bad, first_bad) per pair, row b what check(*pairs[b]) returns."""
+        pairs = list(pairs)
+        count = len(pairs)
+        if count == 0:
+            return np.zeros((0, 2), dtype=np.uint32)
+        el = lambda v: np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4)
+        z = np.ascontiguousarray(np.stack([np.concatenate([el(u), el(x), el(w)]) for u, x, w, _ in pairs]))
+        du, dz, de = self.ctx.upload(np.stack([el(p[0])[0] for p in pairs])), self.ctx.upload(z), None
+        if any(p[3] is not None for p in pairs):
+            de = self.ctx.upload(np.stack([el(p[3]) if p[3] is not None else np.zeros((self.m, 4), dtype=np.uint64) for p in pairs]))
+        ptrs = [tuple(d.ptr for d in trip) for trip in self._dev]
+        return self.ctx.r1cs_check_batch(self.field, ptrs[0], ptrs[1], ptrs[2], self.m, dz.ptr, z.shape[1], count, du.ptr,
+                                         de.ptr if de is not None else 0, self.m).numpy()
 
     def is_sat_relaxed(self, instance: dict, witness: dict) -> bool:
         """R1csShape::is_sat_relaxed (nova/src/relaxed_r1cs.rs:81-114) on the dicts prove() takes and returns: AZ o BZ = u CZ + E.

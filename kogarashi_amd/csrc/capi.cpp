@@ -245,7 +245,7 @@ int kg_hw_queue_setting(void) {
   const char* e = getenv("GPU_MAX_HW_QUEUES");
   return e ? atoi(e) : 0;
 }
-int kg_version(void) { return 6; }      // the round the ABI was last extended in (6: kg_msm_set_small, and since, under the same number, kg_r1cs_prod_batch and kg_groth16_prove_r1cs_batch; 5: kg_msm_host_scalars, kg_commit_host_scalars, kg_tuning_describe; 4: kg_msm_set_groups; 3: kg_init, kg_hw_queue_setting, kg_groth16_prove_sharded)
+int kg_version(void) { return 6; }      // the round the ABI was last extended in (6: kg_msm_set_small, and since, under the same number, kg_r1cs_prod_batch, kg_groth16_prove_r1cs_batch, kg_r1cs_check_batch and kg_groth16_witness_check_batch; 5: kg_msm_host_scalars, kg_commit_host_scalars, kg_tuning_describe; 4: kg_msm_set_groups; 3: kg_init, kg_hw_queue_setting, kg_groth16_prove_sharded)
 
 int kg_experiments_built(void) {
 #ifdef KG_EXPERIMENTS

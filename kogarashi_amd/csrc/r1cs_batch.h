@@ -1,6 +1,7 @@
 // r1cs_batch.h -- the host-only, pure parts of the batched CSR product (kg_r1cs_prod_batch, vec.hip) and of the batched prover's R1CS form
-// (kg_groth16_prove_r1cs_batch, groth16_batch.hip): how a batch of vectors is cut into launches and the argument checks.  No HIP, no
-// context: tests/host/r1cs_batch_host.cpp includes this file alone.
+// (kg_groth16_prove_r1cs_batch, groth16_batch.hip): how a batch of vectors is cut into launches and the argument checks; at the end of the
+// file the same for the batched check (kg_r1cs_check_batch, kg_groth16_witness_check_batch, vec.hip).  No HIP, no context:
+// tests/host/r1cs_batch_host.cpp and tests/host/r1cs_check_batch_host.cpp include this file alone.
 //
 // Layout: vector b of a batch is read at elements [b * z_stride, ...) of d_z (its length is whatever the matrix's columns index: the call
 // cannot know it) and its m row sums go to elements [b * out_stride, b * out_stride + m) of d_out (out_stride >= m, elements of 4 words);
@@ -59,6 +60,57 @@ inline bool g16_r1cs_batch_args_ok(const void* ctx, const void* crs, size_t m, s
   if (count == 0) return true;
   for (const Csr* x : {a, b, c})
     if (!x || !x->d_row_ptr || !x->d_col || !x->d_val) return false;
+  return true;
+}
+
+// ---- the batched satisfiability check (kg_r1cs_check_batch, kg_groth16_witness_check_batch; vec.hip CheckBatchOp) -------------------------
+// Layout: vector b is read at element b * z_stride of d_z (or x_b at b * x_stride of d_x and w_b at b * w_stride of d_w), E_b at element
+// b * e_stride of d_e, u_b is element b of d_u; row i's status byte goes to d_status[b * status_stride + i] (a stride in BYTES) and the
+// vector's summary pair (bad rows, smallest bad row or m) to words 2 b and 2 b + 1 of d_summary.  The chunk rule is the product's.
+constexpr size_t r1cs_check_batch_summary_word(size_t vec) { return 2 * vec; }
+constexpr size_t r1cs_check_batch_status_byte(size_t vec, size_t status_stride, size_t row) { return vec * status_stride + row; }
+
+// The split source's index rule: column j of z = x || w is x[j] for j < l and w[j - l] otherwise (SparseMatrix::prod's wire arithmetic,
+// zkstd/src/matrix.rs:36-48).  constexpr: the kernels call the very function the host test checks.
+struct R1csSplitAt { bool in_x; size_t index; };
+constexpr R1csSplitAt r1cs_split_at(size_t j, size_t l) { return {j < l, j < l ? j : j - l}; }
+
+template <class Csr>
+inline bool r1cs_csr3_ok(const Csr* a, const Csr* b, const Csr* c) {
+  for (const Csr* x : {a, b, c})
+    if (!x || !x->d_row_ptr || !x->d_col || !x->d_val) return false;
+  return true;
+}
+
+// The argument checks of kg_r1cs_check_batch (true = acceptable), made before anything is dereferenced or enqueued.  count == 0 is
+// acceptable with any pointers, m == 0 with any but d_summary (every pair becomes (0, 0)); a null ctx, an unknown field and m >= 2^32 are not
+// acceptable even then.  status_stride counts bytes, the other strides elements of 32 bytes.
+template <class Csr>
+inline bool r1cs_check_batch_args_ok(const void* ctx, int field, const Csr* a, const Csr* b, const Csr* c, size_t m, const void* d_z, size_t z_stride,
+                                     size_t count, const void* d_e, size_t e_stride, const void* d_status, size_t status_stride, const void* d_summary) {
+  if (!ctx || !r1cs_batch_field_ok(field) || m >= ((uint64_t)1 << 32)) return false;
+  if (count == 0) return true;
+  if (!d_summary || count > SIZE_MAX / 8) return false;                                  // count pairs of 32-bit words
+  if (m == 0) return true;
+  if (!r1cs_csr3_ok(a, b, c) || !d_z) return false;
+  if ((d_e && e_stride < m) || (d_status && status_stride < m)) return false;
+  if (z_stride > SIZE_MAX / 32 / count || (d_e && e_stride > SIZE_MAX / 32 / count) || (d_status && status_stride > SIZE_MAX / count)) return false;
+  return true;
+}
+
+// The argument checks of kg_groth16_witness_check_batch: l >= 1, x_stride >= l and w_stride >= m_l_1 are refused even for an empty call (as
+// g16_batch_args_ok refuses them); d_w may be null when the circuit has no witness wire.
+template <class Csr>
+inline bool g16_witness_check_batch_args_ok(const void* ctx, const Csr* a, const Csr* b, const Csr* c, size_t m, size_t l, size_t m_l_1, const void* d_x,
+                                            size_t x_stride, const void* d_w, size_t w_stride, size_t count, const void* d_status, size_t status_stride,
+                                            const void* d_summary) {
+  if (!ctx || m >= ((uint64_t)1 << 32) || l < 1 || x_stride < l || w_stride < m_l_1) return false;
+  if (count == 0) return true;
+  if (!d_summary || count > SIZE_MAX / 8) return false;
+  if (m == 0) return true;
+  if (!r1cs_csr3_ok(a, b, c) || !d_x || (m_l_1 && !d_w)) return false;
+  if (d_status && status_stride < m) return false;
+  if (x_stride > SIZE_MAX / 32 / count || w_stride > SIZE_MAX / 32 / count || (d_status && status_stride > SIZE_MAX / count)) return false;
   return true;
 }
 

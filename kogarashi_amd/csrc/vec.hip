@@ -3,6 +3,8 @@
 // kg_field_vec_op replaces, one GPU thread per element, the reference's limb functions
 // zkstd/src/arithmetic/limbs/bits_256/normal.rs:4-31,34-53,56-80,83-121,124-166,170-184,256-270 and the
 // point-wise polynomial ops groth16/src/poly.rs:168-195.  HBM-bound for add/sub/mul (96 B/element).
+#include <type_traits>
+#include <utility>
 #include "common.h"
 #include "vecops.h"
 #include "host_fp.h"
@@ -101,9 +103,16 @@ __device__ __forceinline__ Fp<P> shfl_xor_f(const Fp<P>& a, int mask) {
 // used as they lie in memory (x * 2^256), so a term is ONE Montgomery product -- z * val * 2^251 -- and the sums live in that
 // "raw product" domain; the caller's next multiplication carries the constant that leaves it (C_FROM_REF for a plain
 // matrix-vector product, the folded constants of cross_term_row).  Converting each coefficient first cost a second product per entry.
-template <class P, int G, int NZ>
+// Z: where the vector's entries come from -- a pointer to its elements, or the batched witness check's split x | w (ZSplit).
+__device__ __forceinline__ void load_z(const uint64_t* __restrict__ z, uint64_t c, uint32_t w[8]) { load_words(z, c, w); }
+struct ZSplit { const uint64_t* x; const uint64_t* w; size_t l; };          // z = x || w read in place: column j is x[j] for j < l, w[j - l] otherwise
+__device__ __forceinline__ void load_z(const ZSplit& z, uint64_t c, uint32_t w[8]) {
+  const R1csSplitAt at = r1cs_split_at(c, z.l);              // one compare and two selects per entry; one load either way
+  load_words(at.in_x ? z.x : z.w, at.index, w);
+}
+template <class P, int G, int NZ, class Z>
 __device__ __forceinline__ void row_dot(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col, const uint64_t* __restrict__ val,
-                                        size_t row, int lane, const uint64_t* __restrict__ z1, const uint64_t* __restrict__ z2, Fp<P> (&sum)[NZ]) {
+                                        size_t row, int lane, const Z& z1, const Z& z2, Fp<P> (&sum)[NZ]) {
 #pragma unroll
   for (int q = 0; q < NZ; ++q) sum[q] = Fp<P>::zero();
   for (uint64_t e = row_ptr[row] + lane; e < row_ptr[row + 1]; e += G) {
@@ -111,10 +120,10 @@ __device__ __forceinline__ void row_dot(const uint64_t* __restrict__ row_ptr, co
     load_words(val, e, wv);
     const Fp<P> v = limbs_from_words<P>(wv);
     const uint64_t c = col[e];
-    load_words(z1, c, wz);
+    load_z(z1, c, wz);
     sum[0] = dot_step(sum[0], limbs_from_words<P>(wz), v);
     if (NZ > 1) {
-      load_words(z2, c, wz);
+      load_z(z2, c, wz);
       sum[NZ - 1] = dot_step(sum[NZ - 1], limbs_from_words<P>(wz), v);
     }
   }
@@ -139,11 +148,20 @@ __device__ __forceinline__ void row_dot(const uint64_t* __restrict__ row_ptr, co
 //                                        only): the row is bad
 //   REPORTS                              bad rows are folded into ws.summary: the lowest bad lane speaks for its 64 rows, a wave of
 //                                        k_rows_wave for the rows it took (the list is in no particular order)
+//   uint32_t* summary()                  optional: the pair to fold into instead of ws.summary (the batched check: one per vector)
 constexpr uint32_t SHORT_ROW = 48;
 constexpr uint32_t HUGE_ROW = 4096;      // beyond: a 1024-lane workgroup per row (the constant-one wire's row of a transposed system: an entry per constraint)
 struct CsrView {
   const uint64_t* row_ptr; const uint64_t* col; const uint64_t* val;
   __device__ __forceinline__ uint64_t len(size_t row) const { return row_ptr[row + 1] - row_ptr[row]; }
+};
+// Where a reporting operation's bad rows are folded: the work space's pair, unless the operation has a summary() of its own (the batched
+// check: a pair per vector, chosen by the block's y index)
+template <class Op, class = void>
+struct SummaryOf { static __device__ __forceinline__ uint32_t* of(const Op&, uint32_t* ws_summary) { return ws_summary; } };
+template <class Op>
+struct SummaryOf<Op, std::void_t<decltype(std::declval<const Op&>().summary())>> {
+  static __device__ __forceinline__ uint32_t* of(const Op& op, uint32_t*) { return op.summary(); }
 };
 template <class Op>
 __global__ void __launch_bounds__(256) k_rows_lane(Op op, size_t m, RowWs ws) {
@@ -156,7 +174,7 @@ __global__ void __launch_bounds__(256) k_rows_lane(Op op, size_t m, RowWs ws) {
     else if (k == 1) ws.list[atomicAdd(ws.count, 1u)] = (uint32_t)row;
     else bad = op.template row<1>(row, 0);
   }
-  if constexpr (Op::REPORTS) summary_fold(ws.summary, bad, (uint32_t)row);
+  if constexpr (Op::REPORTS) summary_fold(SummaryOf<Op>::of(op, ws.summary), bad, (uint32_t)row);
 }
 // (the list as const __restrict__ parameters: handed over as a RowWs, the cross term's and the check's instances take one VGPR more)
 template <class Op>
@@ -171,7 +189,7 @@ __global__ void __launch_bounds__(256) k_rows_wave(Op op, uint32_t* __restrict__
     if (op.template row<64>(row, lane)) { ++n_bad; first = min(first, (uint32_t)row); }
   }
   if constexpr (Op::REPORTS)
-    if (lane == 0 && n_bad != 0) summary_add(summary, n_bad, first);
+    if (lane == 0 && n_bad != 0) summary_add(SummaryOf<Op>::of(op, summary), n_bad, first);
 }
 
 // A HUGE row (more than HUGE_ROW entries) per WORKGROUP: 1024 lanes stride over its entries; wave sums by shuffles, the sixteen wave sums
@@ -276,8 +294,8 @@ struct ProdBatchOp {
 struct Csr3 {
   CsrView A, B, C;
   __device__ __forceinline__ int klass(size_t row) const { return A.len(row) > SHORT_ROW || B.len(row) > SHORT_ROW || C.len(row) > SHORT_ROW; }
-  template <class P, int G, int NZ>
-  __device__ __forceinline__ void dots(size_t row, int lane, const uint64_t* z1, const uint64_t* z2, Fp<P> (&az)[NZ], Fp<P> (&bz)[NZ], Fp<P> (&cz)[NZ]) const {
+  template <class P, int G, int NZ, class Z>
+  __device__ __forceinline__ void dots(size_t row, int lane, const Z& z1, const Z& z2, Fp<P> (&az)[NZ], Fp<P> (&bz)[NZ], Fp<P> (&cz)[NZ]) const {
     row_dot<P, G, NZ>(A.row_ptr, A.col, A.val, row, lane, z1, z2, az);
     row_dot<P, G, NZ>(B.row_ptr, B.col, B.val, row, lane, z1, z2, bz);
     row_dot<P, G, NZ>(C.row_ptr, C.col, C.val, row, lane, z1, z2, cz);
@@ -330,6 +348,59 @@ struct CheckOp : Csr3 {
     return bad;
   }
 };
+
+// kg_r1cs_check_batch / kg_groth16_witness_check_batch: the check for the vectors of one chunk of a batch against ONE shape -- the walker's
+// kernels as they are over a grid whose y index is the vector, as ProdBatchOp runs them: a lane per (short row, vector), a wave per (list
+// entry, vector), the work list built once by the y = 0 blocks of the launch that `lists`.  Every vector folds into its own pair of `sums`
+// (summary(): SummaryOf hands it to the walker), so a lane of k_rows_lane speaks for its 64 rows of vector blockIdx.y and a wave of k_rows_wave
+// for the rows it took of that vector: at most one atomicAdd / atomicMin pair per wave and launch, spread over count addresses.
+// Z: the batch's vector source, vec(b) is what row_dot reads vector b through.  u: count elements in the ABI form, scaled on the device
+// (u_factor; null: us1, the host-scaled one of the single call).  Strides in elements, status_stride in bytes.
+struct ZStrided {
+  const uint64_t* z; size_t stride;
+  __device__ __forceinline__ const uint64_t* vec(size_t b) const { return z + b * stride * 4; }
+  ZStrided from(size_t first) const { return {z + first * stride * 4, stride}; }
+};
+struct ZSplitStrided {
+  const uint64_t* x; size_t x_stride; const uint64_t* w; size_t w_stride, l;
+  __device__ __forceinline__ ZSplit vec(size_t b) const { return {x + b * x_stride * 4, w + b * w_stride * 4, l}; }
+  ZSplitStrided from(size_t first) const { return {x + first * x_stride * 4, x_stride, w + first * w_stride * 4, w_stride, l}; }
+};
+template <class P, class Z>
+struct CheckBatchOp : Csr3 {
+  static constexpr bool REPORTS = true;
+  Z z; const uint64_t* u; Limbs9 us1; const uint64_t* e; size_t e_stride; uint8_t* status; size_t status_stride; uint32_t* sums; bool lists;
+  __device__ __forceinline__ uint32_t* summary() const { return sums + r1cs_check_batch_summary_word(blockIdx.y); }
+  __device__ __forceinline__ int klass(size_t row) const { return lists && blockIdx.y == 0 ? Csr3::klass(row) : 0; }
+  template <int G>
+  __device__ __forceinline__ bool row(size_t row, int lane) const {
+    if (G == 1 && Csr3::klass(row) != 0) return false;      // a list's row: not this lane's
+    const size_t b = blockIdx.y;
+    const auto zb = z.vec(b);
+    Fp<P> az[1], bz[1], cz[1];
+    dots<P, G, 1>(row, lane, zb, zb, az, bz, cz);
+    if (lane != 0) return false;
+    Fp<P> us = Fp<P>::from_const(us1.l), er = Fp<P>::zero();
+    uint32_t wl[8];
+    if (u != nullptr) {
+      load_words(u, b, wl);
+      us = u_factor(limbs_from_words<P>(wl), Fp<P>::from_const(P::C_XT_U));
+    }
+    if (e != nullptr) {
+      load_words(e, b * e_stride + row, wl);
+      er = limbs_from_words<P>(wl);
+    }
+    const bool bad = !is_zero_mod_p(sat_residual_row(az[0], bz[0], cz[0], us, er, Fp<P>::from_const(P::C_XT_HAD)));
+    if (status != nullptr) status[r1cs_check_batch_status_byte(b, status_stride, row)] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
+    return bad;
+  }
+};
+// the batch's one initialising launch: every vector's pair to (0, m), and the two list counters
+__global__ void __launch_bounds__(256) k_check_batch_init(uint32_t* __restrict__ sums, size_t count, uint32_t m, uint32_t* __restrict__ counters) {
+  const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b == 0 && counters != nullptr) { counters[0] = 0; counters[1] = 0; }      // (no rows: no list, no counters)
+  if (b < count) { sums[2 * b] = 0; sums[2 * b + 1] = m; }
+}
 
 // ---- splitmix64 streams (oracle/pyoracle.py stream_at, oracle/kg_oracle.c stream_words) ---------------
 __device__ __forceinline__ uint64_t splitmix_next(uint64_t& s) {
@@ -458,8 +529,8 @@ bool csr3_ok(const kg_csr* a, const kg_csr* b, const kg_csr* cm) {
 Limbs9 scaled(const uint64_t* h_u, bool fr) {
   Limbs9 out;
   uint64_t w64[4];
-  if (fr) { HostFr x = HostFr::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
-  else { HostFq x = HostFq::from_words(h_u); for (int i = 0; i < 10; ++i) x = dbl(x); for (int i = 0; i < 4; ++i) w64[i] = x.v[i]; }
+  if (fr) u_scaled_words<HostFrP>(h_u, w64);
+  else u_scaled_words<HostFqP>(h_u, w64);
   const Fp<FrParams> lim = limbs_from_words<FrParams>(words8(w64).w);        // the spreading is the same for both fields
   for (int k = 0; k < 9; ++k) out.l[k] = lim.l[k];
   return out;
@@ -609,6 +680,58 @@ int kg_r1cs_check(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const 
   by_field(field, [&](auto p) { launch_rows(c->stream, CheckOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z, us, d_e, d_status}, m, ws); });
   KG_HIP(c, hipGetLastError());
   return summary_read(c, ws.summary, out_bad, out_first_bad);
+}
+
+}  // extern "C"
+
+namespace {
+// one shape against `count` vectors read through the source Z (arguments checked by the callers): one initialising launch, then two launches per
+// chunk of 65535 vectors, whatever count is; the first chunk's first launch builds the work list, every later launch reads it.  Nothing is read back.
+template <class Z>
+int check_batch_enqueue(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const Z& z, size_t count, const uint64_t* d_u,
+                        const uint64_t* d_e, size_t e_stride, uint8_t* d_status, size_t status_stride, uint32_t* d_summary) {
+  KG_HIP(c, hipSetDevice(c->device));
+  if (m == 0) {                                            // no row, no list: the pairs alone, (0, 0)
+    hipLaunchKernelGGL(k_check_batch_init, grid256(count), dim3(256), 0, c->stream, d_summary, count, 0u, (uint32_t*)nullptr);
+    KG_HIP(c, hipGetLastError());
+    return KG_OK;
+  }
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  const RowWs ws(c->ws_vec.get(), m);
+  hipLaunchKernelGGL(k_check_batch_init, grid256(count), dim3(256), 0, c->stream, d_summary, count, (uint32_t)m, ws.count);
+  const bool fr = field == KG_FR;
+  const Limbs9 us1 = scaled(fr ? HostFrP::ONE : HostFqP::ONE, fr);
+  by_field(field, [&](auto p) {
+    using Op = CheckBatchOp<decltype(p), Z>;
+    for (size_t i = 0; i < r1cs_batch_chunks(count); ++i) {
+      const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
+      const Op op{{view(a), view(b), view(cm)}, z.from(ch.first), d_u ? d_u + ch.first * 4 : nullptr, us1, d_e ? d_e + ch.first * e_stride * 4 : nullptr, e_stride,
+                  d_status ? d_status + ch.first * status_stride : nullptr, status_stride, d_summary + 2 * ch.first, i == 0};
+      const unsigned y = (unsigned)ch.count;
+      hipLaunchKernelGGL(k_rows_lane<Op>, dim3(grid256(m).x, y), dim3(256), 0, c->stream, op, m, ws);
+      hipLaunchKernelGGL(k_rows_wave<Op>, dim3(r1cs_batch_grid_x(256, ch.count), y), dim3(256), 0, c->stream, op, ws.summary, ws.list, ws.count);
+    }
+  });
+  KG_HIP(c, hipGetLastError());
+  return KG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kg_r1cs_check_batch(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z, size_t z_stride, size_t count,
+                        const uint64_t* d_u, const uint64_t* d_e, size_t e_stride, uint8_t* d_status, size_t status_stride, uint32_t* d_summary) {
+  if (!r1cs_check_batch_args_ok(c, field, a, b, cm, m, d_z, z_stride, count, d_e, e_stride, d_status, status_stride, d_summary)) return KG_ERR_BAD_ARG;
+  if (count == 0) return KG_OK;
+  return check_batch_enqueue(c, field, a, b, cm, m, ZStrided{d_z, z_stride}, count, d_u, d_e, e_stride, d_status, status_stride, d_summary);
+}
+
+int kg_groth16_witness_check_batch(kg_ctx* c, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, size_t l, size_t m_l_1, const uint64_t* d_x,
+                                   size_t x_stride, const uint64_t* d_w, size_t w_stride, size_t count, uint8_t* d_status, size_t status_stride,
+                                   uint32_t* d_summary) {
+  if (!g16_witness_check_batch_args_ok(c, a, b, cm, m, l, m_l_1, d_x, x_stride, d_w, w_stride, count, d_status, status_stride, d_summary)) return KG_ERR_BAD_ARG;
+  if (count == 0) return KG_OK;
+  return check_batch_enqueue(c, KG_FR, a, b, cm, m, ZSplitStrided{d_x, x_stride, d_w, w_stride, l}, count, nullptr, nullptr, 0, d_status, status_stride, d_summary);
 }
 
 int kg_gen_scalars(kg_ctx* c, int field, uint64_t seed, size_t start, size_t n, uint64_t* out) {

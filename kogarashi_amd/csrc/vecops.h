@@ -6,6 +6,7 @@
 // sparse products below stay in that domain until a constant the next multiplication needs anyway takes them out of it.
 #pragma once
 #include "fp29.h"
+#include "host_fp.h"
 
 namespace kg {
 
@@ -47,6 +48,21 @@ KG_HD F sat_residual_row(const F& az, const F& bz, const F& cz, const F& us, con
   const F cu = mul(cz, us);
   return vred(norm(sub<8, 1>(norm(sub<4, 1>(had, cu)), e_raw)));
 }
+// u as it lies in memory (the ABI words as limbs, u * 2^256, any 256-bit value) -> the factor form `us` of sat_residual_row, u * 2^266: one
+// product with xt_u = 2^271 (P::C_XT_U).  The batched check does this on the device, a u per vector; the single call gets the same residue from
+// ten host-side doublings (vec.hip scaled()).  Result: normalised, below 1.01p -- a representative of scaled()'s canonical value.
+template <class F>
+KG_HD F u_factor(const F& u_raw, const F& xt_u) { return mul(u_raw, xt_u); }
+
+// The host's way to the same factor (vec.hip scaled(): kg_r1cs_check, kg_nova_cross_term): u * 2^266 mod p, canonical, as 4 x u64 -- ten
+// modular doublings of the ABI form.  HostP: HostFrP or HostFqP.
+template <class HostP>
+inline void u_scaled_words(const uint64_t* h_u, uint64_t out[4]) {
+  HostFp<HostP> x = HostFp<HostP>::from_words(h_u);
+  for (int i = 0; i < 10; ++i) x = dbl(x);
+  x.to_words(out);
+}
+
 // Is a residual as sat_residual_row leaves it zero in the field?  The value is the canonical residue or that plus p (vred's quotient
 // estimate may be one short), never more: a row that holds arrives as 0 or as p.  BOTH occur -- the lazy value of a satisfied row is k p
 // with 6 <= k <= 13 and vred takes off k p or (k - 1) p, decided by the top limb alone (a row with no entries and E = 0 is the lazy

@@ -36,6 +36,7 @@ EXPORTS = [
     "kg_commit_batch", "kg_commit_batch_plan",
     "kg_groth16_prove_batch", "kg_groth16_prove_batch_plan",
     "kg_r1cs_prod_batch", "kg_groth16_prove_r1cs_batch",
+    "kg_r1cs_check_batch", "kg_groth16_witness_check_batch",
 ]
 
 
@@ -121,6 +122,12 @@ def load():
         _lib.kg_groth16_prove_r1cs_batch.restype = C.c_int
         _lib.kg_groth16_prove_r1cs_batch.argtypes = [C.c_void_p, C.POINTER(Groth16Crs), C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_void_p, C.c_size_t,
                                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        _lib.kg_r1cs_check_batch.restype = C.c_int
+        _lib.kg_r1cs_check_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        _lib.kg_groth16_witness_check_batch.restype = C.c_int
+        _lib.kg_groth16_witness_check_batch.argtypes = [C.c_void_p, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                        C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
     return _lib
 
 
@@ -475,6 +482,35 @@ class Context:
         self._chk(self._lib.kg_r1cs_check(self._h, int(field), C.byref(ca), C.byref(cb), C.byref(cc), C.c_size_t(m), _vp(z), hu, _vp(e), _vp(status),
                                           C.byref(bad), C.byref(first)), "kg_r1cs_check")
         return int(bad.value), int(first.value)
+
+    def r1cs_check_batch(self, field: int, a, b, c, m: int, z: int, z_stride: int, count: int, u: int = 0, e: int = 0, e_stride: int = 0, status: int = 0,
+                         status_stride: int = 0, summary=None):
+        """kg_r1cs_check_batch: kg_r1cs_check for count vectors against one shape.  Everything is a device pointer or a stride: vector b at
+        element b * z_stride of z, E_b at element b * e_stride of e (0: E = 0), u_b element b of u (0: u = 1), row i's status byte at
+        status[b * status_stride + i] (a stride in bytes; 0: no status bytes).  Returns the device array (count, 2) of uint32 pairs (bad
+        rows, first bad row or m) -- `summary` when one is handed in.  Enqueued on the context's stream: valid in stream order, numpy() waits."""
+        mk = lambda t: Csr(_vp(t[0]), _vp(t[1]), _vp(t[2]))
+        ca, cb, cc = mk(a), mk(b), mk(c)
+        if summary is None:
+            summary = self.empty((count, 2), dtype=np.uint32)
+        self._chk(self._lib.kg_r1cs_check_batch(self._h, int(field), C.byref(ca), C.byref(cb), C.byref(cc), C.c_size_t(m), _vp(z), C.c_size_t(z_stride),
+                                                C.c_size_t(count), _vp(u), _vp(e), C.c_size_t(e_stride), _vp(status), C.c_size_t(status_stride),
+                                                _vp(summary.ptr)), "kg_r1cs_check_batch")
+        return summary
+
+    def groth16_witness_check_batch(self, a, b, c, m: int, l: int, m_l_1: int, x: int, x_stride: int, w: int, w_stride: int, count: int, status: int = 0,
+                                    status_stride: int = 0, summary=None):
+        """kg_groth16_witness_check_batch: R1cs::is_sat for count witnesses x_b || w_b read in place from the arrays
+        groth16_prove_r1cs_batch takes (device pointers, strides in elements).  Returns the device array (count, 2) of uint32 pairs (bad
+        rows, first bad row or m).  Enqueued on the context's stream."""
+        mk = lambda t: Csr(_vp(t[0]), _vp(t[1]), _vp(t[2]))
+        ca, cb, cc = mk(a), mk(b), mk(c)
+        if summary is None:
+            summary = self.empty((count, 2), dtype=np.uint32)
+        self._chk(self._lib.kg_groth16_witness_check_batch(self._h, C.byref(ca), C.byref(cb), C.byref(cc), C.c_size_t(m), C.c_size_t(l), C.c_size_t(m_l_1),
+                                                           _vp(x), C.c_size_t(x_stride), _vp(w), C.c_size_t(w_stride), C.c_size_t(count), _vp(status),
+                                                           C.c_size_t(status_stride), _vp(summary.ptr)), "kg_groth16_witness_check_batch")
+        return summary
 
     def fixed_base_mul(self, curve: int, k: int, n: int, out_xy: int, out_inf: int):
         self._chk(self._lib.kg_fixed_base_mul(self._h, curve, _vp(k), C.c_size_t(n), _vp(out_xy), _vp(out_inf)), "kg_fixed_base_mul")
