@@ -123,6 +123,18 @@ int kg_field_vec_op(kg_ctx* ctx, int field, int op, const uint64_t* d_a, const u
  * nova/src/relaxed_r1cs/witness.rs:56-70 (W = W1 + r W2, E = E1 + r T + r^2 E2) and instance.rs:81-101 (x = x1 + r x2);
  * Fr for the bn254 driver, Fq for the Grumpkin driver (nova/src/driver.rs:9-42). */
 int kg_field_vec_axpy(kg_ctx* ctx, int field, const uint64_t* d_a, const uint64_t* h_s, const uint64_t* d_b, uint64_t* d_out, size_t n);
+/* kg_field_vec_axpy for count vectors in one call, each with a scalar of its own that lives on the DEVICE: out_b[i] = a_b[i] + s_b * b_b[i],
+ * i < n.  Vector b reads d_a + b * a_stride * 4 words and d_b + b * b_stride * 4 words and writes d_out + b * out_stride * 4 words (strides
+ * in ELEMENTS, each >= n); s_b = d_s[b] (4 words, the ABI's Montgomery form).  The elements between two vectors are neither read nor
+ * written.  d_out may alias d_a EXACTLY (the same pointer and the same stride) and nothing else.  Output b is bit-identical to
+ * kg_field_vec_axpy(ctx, field, a_b, &s_b, b_b, out_b, n).  With z = (u | x | w) and z2 beginning with one, z1 += r z2 folds u, x and W of a
+ * Nova step in one pass.
+ * The batch family's stream rule: ENQUEUED on the context's stream, does not block, reads nothing back, starts no worker thread.  One launch
+ * whatever count is (a lane per (vector, element) over the flattened index: no grid dimension bounds count).
+ * n == 0 or count == 0: KG_OK, nothing enqueued.  KG_ERR_BAD_ARG, decided before anything is dereferenced or enqueued: a null ctx; an unknown
+ * field; a stride below n; and for n > 0 and count > 0 a null array, a count * stride * 32 beyond size_t. */
+int kg_field_vec_axpy_batch(kg_ctx* ctx, int field, const uint64_t* d_a, size_t a_stride, const uint64_t* d_s, const uint64_t* d_b,
+                            size_t b_stride, uint64_t* d_out, size_t out_stride, size_t n, size_t count);
 /* out[i] = start * base^i, i < n  (start, base: one element each, HOST pointers): the `scan(one, *= g)` tables of
  * fft.rs:35-41,56-70 and the powers of tau of the trusted setup, groth16/src/zksnark.rs:44-49. */
 int kg_field_powers(kg_ctx* ctx, int field, const uint64_t* h_start, const uint64_t* h_base, uint64_t* d_out, size_t n);
@@ -330,6 +342,27 @@ int kg_sharded_key_commit(kg_sharded_key* key, const uint64_t* h_scalars, size_t
  * used by PedersenCommitment::new, nova/src/pedersen.rs:10-13).  d_k: n scalars of the curve's scalar field;
  * d_out_xy: n x (8 | 16) words; d_out_inf: n flags (k = 0 gives the identity, stored as (0, 1) + flag 1). */
 int kg_fixed_base_mul(kg_ctx* ctx, int curve, const uint64_t* d_k, size_t n, uint64_t* d_out_xy, uint8_t* d_out_inf);
+/* out[j] = affine(P[j] + k[j / per_scalar] * Q[j]), j < count, results left on the device: the instance fold of Nova's NIFS
+ * (nova/src/relaxed_r1cs/instance.rs:81-101: commit_w = commit_w1 + r commit_w2, commit_e = commit_e1 + r commit_T) for a batch of folds --
+ * the pairs (commit_w, commit_e) interleaved with per_scalar = 2, so that a fold's two chains run in one launch.  curve: KG_G1 or
+ * KG_GRUMPKIN (KG_G2: KG_ERR_BAD_ARG, Nova has no G2).  d_p_xy, d_q_xy, d_out_xy: count x 8 words, affine; d_p_inf, d_q_inf: count identity
+ * flags, either may be NULL (no identities); d_out_inf: count flags, an identity result is stored as (0, 1) + flag 1, as kg_fixed_base_mul
+ * writes it.  d_k: ceil(count / per_scalar) scalars of the curve's scalar field (Fr for G1, Fq for Grumpkin) in the ABI's Montgomery form;
+ * per_scalar >= 1.  d_out_xy / d_out_inf may alias d_p_xy / d_p_inf EXACTLY and nothing else.
+ * The batch family's stream rule: ENQUEUED on the context's stream, does not block, reads nothing back, starts no worker thread.  One
+ * launch: a lane per point, a 255-step double-and-add chain each, whatever the scalar -- a fixed cost per call.
+ * count == 0: KG_OK, nothing enqueued.  KG_ERR_BAD_ARG, decided before anything is dereferenced or enqueued: a null ctx; a curve other than
+ * KG_G1 and KG_GRUMPKIN; per_scalar == 0; and for count > 0 a null d_p_xy, d_q_xy, d_k, d_out_xy or d_out_inf, count >= 2^37.
+ * Measured (chain circuit over Fr / G1; profiles/nova_fold_batch_timing.txt: a whole batch of folds -- kg_nova_cross_term_batch,
+ * kg_commit_batch, the read-back of count points, two kg_field_vec_axpy_batch, this call, one sync -- against the loop of single entries,
+ * medians of alternating rounds): 256 pairs of 2^4 / 2^10 / 2046 / 2^14 constraints 5.28 / 9.17 / 12.50 / 66.66 ms against 83.70 / 95.07 /
+ * 100.45 / 121.87 ms; 64 pairs 4.56 / 5.37 / 6.06 / 19.10 against 20.46 / 26.54 / 25.02 / 30.22; 16 pairs 4.49 / 4.69 / 4.69 / 7.29 against
+ * 5.22 / 5.95 / 6.27 / 7.59; 4 pairs 4.64 / 4.31 / 4.42 / 4.33 against 1.30 / 1.50 / 1.55 / 1.89: the batch LOSES below ~16 pairs.  This call
+ * alone is 3.0 .. 3.2 ms + sync whatever count is between 8 and 512 points (a two-point kg_msm_host: 0.09 ms, break-even at ~32 points); the
+ * cross-term and axpy batches have no such floor (0.035 .. 0.09 and 0.017 .. 0.036 ms for m <= 2046, never slower than their loops). */
+int kg_points_muladd_batch(kg_ctx* ctx, int curve, const uint64_t* d_p_xy, const uint8_t* d_p_inf, const uint64_t* d_q_xy,
+                           const uint8_t* d_q_inf, const uint64_t* d_k, size_t per_scalar, size_t count, uint64_t* d_out_xy,
+                           uint8_t* d_out_inf);
 
 /* ---- Groth16 prover --------------------------------------------------------------------------------
  * groth16/src/prover.rs:20-99 Prover::create_proof after circuit synthesis.  The CRS (groth16/src/params.rs:6-28)
@@ -475,6 +508,24 @@ int kg_r1cs_prod_batch(kg_ctx* ctx, int field, const uint64_t* d_row_ptr, const 
  * read once, the six products stay in registers. */
 int kg_nova_cross_term(kg_ctx* ctx, int field, const kg_csr* a, const kg_csr* b, const kg_csr* c, size_t m, const uint64_t* d_z1,
                        const uint64_t* d_z2, const uint64_t* h_u1, const uint64_t* h_u2, uint64_t* d_out);
+/* kg_nova_cross_term for count pairs against ONE shape in one call: the first phase of a batch of Nova folds (kg_commit_batch over the T
+ * rows follows on the same stream).  Pair b reads z1_b at d_z1 + b * z1_stride * 4 words and z2_b at d_z2 + b * z2_stride * 4 words and
+ * writes the m elements of T_b at d_out + b * out_stride * 4 words: strides in ELEMENTS, out_stride >= m; the elements between two outputs
+ * are neither read nor written.  d_u1, d_u2: DEVICE, count elements each in the ABI's Montgomery form, u1_b = d_u1[b]; NULL for either: one
+ * for every pair (the reference always passes u2 = 1).  T_b is bit-identical to kg_nova_cross_term on (z1_b, z2_b, u1_b, u2_b).
+ * The batch family's stream rule: ENQUEUED on the context's stream, does not block, reads nothing back, starts no worker thread; outputs are
+ * valid in stream order or after kg_ctx_sync.  One memset per call, then two launches per chunk of 65535 pairs whatever count is: a lane
+ * per (short row, pair), a wave per (listed row, pair).  A row is long when it has more than 48 entries in any of the three matrices -- the
+ * shape alone decides, so the work list is built once, by the first chunk's first launch.  Each pair's u is scaled on the device; each
+ * matrix row is read once per pair, the six row sums stay in registers.
+ * PRECONDITIONS as for kg_nova_cross_term and kg_r1cs_prod_batch (rows ascend, columns inside each vector, canonical values, the z strides
+ * trusted).
+ * count == 0 or m == 0: KG_OK, nothing enqueued.  KG_ERR_BAD_ARG, decided before anything is dereferenced or enqueued: a null ctx; an
+ * unknown field; m >= 2^32; out_stride < m; and for count > 0 and m > 0 a null kg_csr or member array, a null d_z1, d_z2 or d_out, a
+ * count * stride * 32 beyond size_t. */
+int kg_nova_cross_term_batch(kg_ctx* ctx, int field, const kg_csr* a, const kg_csr* b, const kg_csr* c, size_t m, const uint64_t* d_z1,
+                             size_t z1_stride, const uint64_t* d_z2, size_t z2_stride, size_t count, const uint64_t* d_u1,
+                             const uint64_t* d_u2, uint64_t* d_out, size_t out_stride);
 /* ---- R1CS satisfiability ----------------------------------------------------------------------------
  * Does z satisfy the constraints?  Row i holds iff (A z)_i * (B z)_i = u * (C z)_i + E_i (mod p), field = KG_FR or KG_FQ.  With h_u and d_e
  * both NULL this is R1cs::is_sat (zkstd/src/r1cs.rs:62-77) and the constraint half of R1csShape::is_sat (nova/src/relaxed_r1cs.rs:117-146;

@@ -487,6 +487,52 @@ class R1csShape {
     out.download(t.data());
     return t;
   }
+  // compute_cross_term for several pairs against this shape in one kg_nova_cross_term_batch: zs1 / zs2 hold the z vectors one after another
+  // (each zs1.size() / us1.size() elements), us1 one u per pair; u2 = 1 for every pair, as the reference passes it.  Returns the T rows one
+  // after another, m() elements each.
+  std::vector<Fe> compute_cross_term_batch(const std::vector<Fe>& zs1, const std::vector<Fe>& zs2, const std::vector<Fe>& us1) const {
+    const size_t count = us1.size();
+    if (count == 0) return {};
+    if (zs1.size() % count != 0 || zs2.size() != zs1.size()) throw std::invalid_argument("R1csShape: one z1, one z2 and one u1 per pair");
+    const size_t nz = zs1.size() / count;
+    if (m_ && nz <= max_col_) throw std::out_of_range("R1csShape: z is shorter than the largest column index");
+    std::vector<Fe> t(count * m_);
+    if (m_ == 0) return t;
+    DeviceBuffer d1(c_, zs1.data(), zs1.size() * 32), d2(c_, zs2.data(), zs2.size() * 32), du(c_, us1.data(), count * 32), out(c_, count * m_ * 32);
+    c_.check(kg_nova_cross_term_batch(c_.raw(), field_, &csr_[0], &csr_[1], &csr_[2], m_, d1.as<uint64_t>(), nz, d2.as<uint64_t>(), nz, count, du.as<uint64_t>(),
+                                      nullptr, out.as<uint64_t>(), m_), "kg_nova_cross_term_batch");
+    out.download(t.data());
+    return t;
+  }
+  // The two folds behind it, over this shape's field: as_b + s_b * bs_b for ss.size() vectors of as.size() / ss.size() elements
+  // (kg_field_vec_axpy_batch; witness.rs:56-70) ...
+  std::vector<Fe> vec_axpy_batch(const std::vector<Fe>& as, const std::vector<Fe>& ss, const std::vector<Fe>& bs) const {
+    const size_t count = ss.size();
+    if (count == 0 || as.empty()) return {};
+    if (as.size() % count != 0 || bs.size() != as.size()) throw std::invalid_argument("R1csShape: one a, one b and one scalar per vector");
+    const size_t n = as.size() / count;
+    DeviceBuffer da(c_, as.data(), as.size() * 32), db(c_, bs.data(), bs.size() * 32), ds(c_, ss.data(), count * 32);
+    c_.check(kg_field_vec_axpy_batch(c_.raw(), field_, da.as<uint64_t>(), n, ds.as<uint64_t>(), db.as<uint64_t>(), n, da.as<uint64_t>(), n, n, count),
+             "kg_field_vec_axpy_batch");
+    std::vector<Fe> r(as.size());
+    da.download(r.data());
+    return r;
+  }
+  // ... and P_j + k_{j / per_scalar} Q_j on the field's curve (KG_G1 for KG_FR, KG_GRUMPKIN for KG_FQ; kg_points_muladd_batch;
+  // instance.rs:81-101): affine points of 8 words with one flag each (1: the identity), results in p_xy / p_inf.
+  void points_muladd_batch(std::vector<uint64_t>& p_xy, std::vector<uint8_t>& p_inf, const std::vector<uint64_t>& q_xy, const std::vector<uint8_t>& q_inf,
+                           const std::vector<Fe>& ks, size_t per_scalar) const {
+    const size_t count = p_inf.size();
+    if (count == 0) return;
+    if (per_scalar == 0 || p_xy.size() != 8 * count || q_xy.size() != 8 * count || q_inf.size() != count || ks.size() * per_scalar < count)
+      throw std::invalid_argument("R1csShape: 8 words and a flag per point, a scalar per per_scalar points");
+    DeviceBuffer dp(c_, p_xy.data(), count * 64), dpi(c_, p_inf.data(), count), dq(c_, q_xy.data(), count * 64), dqi(c_, q_inf.data(), count),
+        dk(c_, ks.data(), ks.size() * 32);
+    c_.check(kg_points_muladd_batch(c_.raw(), field_ == KG_FR ? KG_G1 : KG_GRUMPKIN, dp.as<uint64_t>(), dpi.as<uint8_t>(), dq.as<uint64_t>(), dqi.as<uint8_t>(),
+                                    dk.as<uint64_t>(), per_scalar, count, dp.as<uint64_t>(), dpi.as<uint8_t>()), "kg_points_muladd_batch");
+    dp.download(p_xy.data());
+    dpi.download(p_inf.data());
+  }
   // R1cs::is_sat (zkstd/src/r1cs.rs:62-77) and the constraint half of R1csShape::is_sat (nova/src/relaxed_r1cs.rs:117-146): AZ o BZ = CZ;
   // is_sat_relaxed (relaxed_r1cs.rs:81-114): AZ o BZ = u CZ + E.  One kg_r1cs_check each: bad = the number of rows that do not hold,
   // first_bad = the smallest of them (m() when bad == 0).  status: per-row 0 / KG_ROW_UNSAT, filled when non-null.

@@ -551,6 +551,81 @@ class NovaProver:
                     "commit_e": fold_point(instance1["commit_e"], commit_t), "u": ux[0].copy(), "x": ux[1:].copy()}
         return instance, {"w": dw1.numpy(), "e": de1.numpy()}, commit_t
 
+    # ---- a batch of folds: two enqueued phases with the transcript's challenges in between --------------------------------------------
+    def fold_begin(self, pairs):
+        """The first phase of prove() for a list of (instance1, witness1, instance2, witness2) in the dict shapes prove() takes, all of
+        this shape: the z1 = (u | x1 | w1), z2 = (1 | x2 | w2) and E1 arrays are packed and uploaded once, the cross terms
+        (kg_nova_cross_term_batch) and their commitments (kg_commit_batch over the T rows, n = min(m, len(ck))) are enqueued, and only
+        the count commitments are read back.  Returns (state, commit_ts): commit_ts is the list of (xy, inf) the caller's transcript
+        hashes into the challenges fold_end takes; state is handed to fold_end unchanged.
+        Beyond 2048 constraints kg_commit_batch runs its blocking loop of single commitments (kg_commit_batch_plan reports 0 groups):
+        the result is the same, the commitments are then not one launch group."""
+        c, fd, cid, m = self.ctx, self.field, self.ck.cid, self.m
+        pairs = list(pairs)
+        count = len(pairs)
+        if count == 0:
+            return {"count": 0}, []
+        el = lambda v: np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4)
+        one = self._one()
+        z1 = np.ascontiguousarray(np.stack([np.concatenate([el(i1["u"]), el(i1["x"]), el(w1["w"])]) for i1, w1, _, _ in pairs]))
+        z2 = np.ascontiguousarray(np.stack([np.concatenate([one.reshape(1, 4), el(i2["x"]), el(w2["w"])]) for _, _, i2, w2 in pairs]))
+        if z1.shape != z2.shape:
+            raise ValueError("the two sides of a fold have different numbers of instance or witness values")
+        e1 = np.ascontiguousarray(np.stack([el(w1["e"]) for _, w1, _, _ in pairs]))
+        if e1.shape[1] != m:
+            raise ValueError("an error vector whose length is not the shape's number of constraints")
+        nz, lx = z1.shape[1], len(el(pairs[0][0]["x"]))
+        dz1, dz2, de1, du1, dt = c.upload(z1), c.upload(z2), c.upload(e1), c.upload(np.ascontiguousarray(z1[:, 0])), c.empty((count, max(m, 1), 4))
+        ptrs = [tuple(d.ptr for d in trip) for trip in self._dev]
+        c.nova_cross_term_batch(fd, ptrs[0], ptrs[1], ptrs[2], m, dz1.ptr, nz, dz2.ptr, nz, count, du1.ptr, 0, dt.ptr, m)
+        n = min(m, self.ck.len)
+        d_ct, d_ct_inf = c.empty((count, 8)), c.empty((count,), dtype=np.uint8)
+        c.commit_batch(cid, self.ck._g.ptr, self.ck._inf.ptr if self.ck._inf else 0, dt.ptr, n, count, m, d_ct.ptr, d_ct_inf.ptr)
+        ct, ct_inf = d_ct.numpy(), d_ct_inf.numpy()              # the one read-back of the phase: count points
+        # the point fold's operands, interleaved per pair: P = (commit_w1, commit_e1), Q = (commit_w2, commit_T)
+        pxy, qxy = np.zeros((2 * count, 8), dtype=np.uint64), np.zeros((2 * count, 8), dtype=np.uint64)
+        pinf, qinf = np.zeros(2 * count, dtype=np.uint8), np.zeros(2 * count, dtype=np.uint8)
+        for b, (i1, _, i2, _) in enumerate(pairs):
+            for dst, dinf, j, pt in ((pxy, pinf, 2 * b, i1["commit_w"]), (pxy, pinf, 2 * b + 1, i1["commit_e"]), (qxy, qinf, 2 * b, i2["commit_w"])):
+                dinf[j] = int(bool(pt[1]))
+                if not dinf[j]:
+                    dst[j] = np.ascontiguousarray(pt[0], dtype=np.uint64).reshape(8)
+            qxy[2 * b + 1], qinf[2 * b + 1] = ct[b], ct_inf[b]
+        state = {"count": count, "nz": nz, "lx": lx, "z1": dz1, "z2": dz2, "e1": de1, "t": dt, "pxy": c.upload(pxy), "pinf": c.upload(pinf),
+                 "qxy": c.upload(qxy), "qinf": c.upload(qinf), "commit_t": [(ct[b].copy(), int(ct_inf[b])) for b in range(count)]}
+        return state, state["commit_t"]
+
+    def fold_end(self, state, rs):
+        """The second phase: rs is a (count, 4) array of challenges, one per pair of fold_begin.  Uploads them and enqueues z1 += r z2
+        (u, x and W in one pass: z = (u | x | w) and z2 begins with one), E1 += r T (kg_field_vec_axpy_batch) and the 2 count point folds
+        (commit_w1 + r commit_w2, commit_e1 + r commit_T: kg_points_muladd_batch, per_scalar = 2); then reads the folded pairs back.
+        Returns the list of (instance, witness, commit_t) in prove()'s shapes."""
+        c, fd, cid, m = self.ctx, self.field, self.ck.cid, self.m
+        count = state["count"]
+        if count == 0:
+            return []
+        rs = np.ascontiguousarray(rs, dtype=np.uint64).reshape(count, 4)
+        dr = c.upload(rs)
+        nz, lx = state["nz"], state["lx"]
+        c.field_vec_axpy_batch(fd, state["z1"].ptr, nz, dr.ptr, state["z2"].ptr, nz, state["z1"].ptr, nz, nz, count)
+        c.field_vec_axpy_batch(fd, state["e1"].ptr, m, dr.ptr, state["t"].ptr, m, state["e1"].ptr, m, m, count)
+        c.points_muladd_batch(cid, state["pxy"].ptr, state["pinf"].ptr, state["qxy"].ptr, state["qinf"].ptr, dr.ptr, 2, 2 * count, state["pxy"].ptr,
+                              state["pinf"].ptr)
+        z, e, xy, inf = state["z1"].numpy(), state["e1"].numpy(), state["pxy"].numpy(), state["pinf"].numpy()
+        out = []
+        for b in range(count):
+            instance = {"commit_w": (xy[2 * b].copy(), int(inf[2 * b])), "commit_e": (xy[2 * b + 1].copy(), int(inf[2 * b + 1])),
+                        "u": z[b, 0].copy(), "x": z[b, 1:1 + lx].copy()}
+            out.append((instance, {"w": z[b, 1 + lx:].copy(), "e": e[b].copy()}, state["commit_t"][b]))
+        return out
+
+    def prove_batch(self, pairs, r):
+        """prove() for a list of pairs in two enqueued phases (fold_begin, fold_end).  r: a (count, 4) array of challenges, or a callable
+        that maps the list of commit_t to such an array -- the place of the caller's transcript.  Element b equals
+        prove(*pairs[b], r[b]) in every word and flag."""
+        state, commit_ts = self.fold_begin(pairs)
+        return self.fold_end(state, r(commit_ts) if callable(r) else r)
+
     def check(self, u, x, w, e=None) -> tuple[int, int]:
         """(bad, first_bad) of kg_r1cs_check over z = (u | x | w): the rows i with (A z)_i (B z)_i != u (C z)_i + E_i and the first of
         them (m when there is none).  e: (m, 4) host array, a DeviceArray (e.g. a fold's output, still in flight on the context's

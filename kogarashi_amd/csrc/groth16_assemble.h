@@ -43,6 +43,16 @@ KG_HD XYZZ<F> g16_mul2(const XYZZ<F>& p, const uint32_t k1[8], const XYZZ<F>& q,
   return g16_mul2_ops<F>(ops, k1, k2);
 }
 
+// P + k Q -- the instance fold of a Nova step (nova/src/relaxed_r1cs/instance.rs:81-101), points_fold.hip -- is the chain with k1 = 1: bit 0
+// of k1 brings P in at the last step.  k_ref: the scalar in the ABI's Montgomery form over the curve's scalar field (parameters SP).
+template <class F, class SP, class Ops>
+KG_HD XYZZ<F> muladd_chain_ops(const Ops& ops, const uint32_t k_ref[8]) {
+  uint32_t ki[8];
+  ref_to_int<SP>(k_ref, ki);
+  const uint32_t one[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+  return g16_mul2_ops<F>(ops, one, ki);
+}
+
 // The scalars of a role as canonical integers, from r and s in the ABI's Montgomery form; r s is one field product.  Every role computes
 // all of them and selects.
 KG_HD void g16_chain_scalars(int role, const uint32_t r_ref[8], const uint32_t s_ref[8], uint32_t k1[8], uint32_t k2[8]) {

@@ -14,13 +14,12 @@
 #include "groth16_batch.h"
 #include "r1cs_batch.h"
 #include "groth16_assemble.h"
+#include "chain_lds.h"
 #include <climits>
 
 using namespace kg;
 
 namespace {
-
-constexpr int G16_NT = 64;                               // one wave per workgroup: the chain kernels use no barrier
 
 // ---- fill: padded rows and z ------------------------------------------------------------------------------------------------------------
 struct G16FillArgs {
@@ -53,48 +52,9 @@ __global__ void __launch_bounds__(256) k_g16_fill(G16FillArgs a) {
 }
 
 // ---- the assembly ------------------------------------------------------------------------------------------------------------------------
-// the chain's three operands in LDS, one column per lane (word k of operand o at lds[(o * NW + k) * G16_NT + lane]: no bank conflicts)
-template <class F>
-struct G16LdsOps {
-  static constexpr int NW = PointIO<F>::NW;
-  uint32_t* col;                                         // lds + lane
-  __device__ __forceinline__ void put(int o, const XYZZ<F>& p) const { PointIO<F>::store(col + (size_t)o * NW * G16_NT, G16_NT, 0, p); }
-  __device__ __forceinline__ XYZZ<F> operator()(int sel) const { return PointIO<F>::load(col + (size_t)(sel - 1) * NW * G16_NT, G16_NT, 0); }
-};
-
+// (the LDS operand columns, the point loaders and the affine writer: chain_lds.h, shared with points_fold.hip)
 struct G16VkG1 { uint32_t alpha[16], beta1[16], delta1[16]; };       // affine x | y, ABI words
 struct G16VkG2 { uint32_t beta2[32], delta2[32]; };
-
-__device__ __forceinline__ XYZZ<Fq> g16_g1_point(const uint32_t w[16], bool inf) {
-  if (inf) return XYZZ<Fq>::identity();
-  return from_affine(Affine<Fq>{from_ref<FqParams>(w), from_ref<FqParams>(w + 8)});
-}
-__device__ __forceinline__ XYZZ<Fq2> g16_g2_point(const uint32_t w[32], bool inf) {
-  if (inf) return XYZZ<Fq2>::identity();
-  return from_affine(Affine<Fq2>{{from_ref<FqParams>(w), from_ref<FqParams>(w + 8)}, {from_ref<FqParams>(w + 16), from_ref<FqParams>(w + 24)}});
-}
-template <class P>
-__device__ __forceinline__ void g16_put(const Fp<P>& a, uint64_t* dst) {
-  uint32_t w[8];
-  to_ref(a, w);
-  store_words(dst, 0, w);
-}
-template <class G>
-__device__ __forceinline__ void g16_put(const Fp2<G>& a, uint64_t* dst) { g16_put(a.c0, dst); g16_put(a.c1, dst + 4); }
-// XYZZ -> affine ABI words and flag; the identity is (0, 1) + flag 1, as kg_fixed_base_mul writes it
-template <class F, int E64>
-__device__ __forceinline__ void g16_put_affine(const XYZZ<F>& p, uint64_t* dst, uint8_t* inf) {
-  Affine<F> a;
-  if (to_affine(p, a)) {
-    g16_put(a.x, dst);
-    g16_put(a.y, dst + E64);
-    *inf = 0;
-  } else {
-    g16_put(F::zero(), dst);
-    g16_put(F::one(), dst + E64);
-    *inf = 1;
-  }
-}
 
 // Lane t = 4 * proof + role runs chain `role` (0 .. 3) of its proof; the result goes to column t of `chains` (raw limbs, structure of
 // arrays over the 4 g lanes).  The lanes differ in data only: every lane reads its proof's two sums and picks its operands word by word.

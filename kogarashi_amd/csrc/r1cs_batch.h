@@ -1,7 +1,8 @@
 // r1cs_batch.h -- the host-only, pure parts of the batched CSR product (kg_r1cs_prod_batch, vec.hip) and of the batched prover's R1CS form
 // (kg_groth16_prove_r1cs_batch, groth16_batch.hip): how a batch of vectors is cut into launches and the argument checks; at the end of the
-// file the same for the batched check (kg_r1cs_check_batch, kg_groth16_witness_check_batch, vec.hip).  No HIP, no context:
-// tests/host/r1cs_batch_host.cpp and tests/host/r1cs_check_batch_host.cpp include this file alone.
+// file the same for the batched check (kg_r1cs_check_batch, kg_groth16_witness_check_batch, vec.hip) and for the batched cross term
+// (kg_nova_cross_term_batch, vec.hip).  No HIP, no context: tests/host/r1cs_batch_host.cpp, tests/host/r1cs_check_batch_host.cpp and
+// tests/host/nova_fold_batch_host.cpp include this file alone.
 //
 // Layout: vector b of a batch is read at elements [b * z_stride, ...) of d_z (its length is whatever the matrix's columns index: the call
 // cannot know it) and its m row sums go to elements [b * out_stride, b * out_stride + m) of d_out (out_stride >= m, elements of 4 words);
@@ -111,6 +112,22 @@ inline bool g16_witness_check_batch_args_ok(const void* ctx, const Csr* a, const
   if (!r1cs_csr3_ok(a, b, c) || !d_x || (m_l_1 && !d_w)) return false;
   if (d_status && status_stride < m) return false;
   if (x_stride > SIZE_MAX / 32 / count || w_stride > SIZE_MAX / 32 / count || (d_status && status_stride > SIZE_MAX / count)) return false;
+  return true;
+}
+
+// ---- the batched Nova cross term (kg_nova_cross_term_batch; vec.hip CrossBatchOp) -------------------------------------------------------
+// Layout: pair b reads z1_b at element b * z1_stride of d_z1 and z2_b at element b * z2_stride of d_z2 and writes the m elements of T_b at
+// element b * out_stride of d_out (out_stride >= m); u1_b and u2_b are element b of d_u1 / d_u2 (null: one for every pair -- not looked at
+// here).  The chunk rule is the product's.
+// The argument checks (true = acceptable), made before anything is dereferenced or enqueued.  An empty call (count == 0 or m == 0) is
+// acceptable with any pointers; a null ctx, an unknown field, m >= 2^32 and out_stride < m are not acceptable even then.
+template <class Csr>
+inline bool nova_cross_batch_args_ok(const void* ctx, int field, const Csr* a, const Csr* b, const Csr* c, size_t m, const void* d_z1, size_t z1_stride,
+                                     const void* d_z2, size_t z2_stride, size_t count, const void* d_out, size_t out_stride) {
+  if (!ctx || !r1cs_batch_field_ok(field) || m >= ((uint64_t)1 << 32) || out_stride < m) return false;
+  if (r1cs_batch_empty(m, count)) return true;
+  if (!r1cs_csr3_ok(a, b, c) || !d_z1 || !d_z2 || !d_out) return false;
+  if (z1_stride > SIZE_MAX / 32 / count || z2_stride > SIZE_MAX / 32 / count || out_stride > SIZE_MAX / 32 / count) return false;
   return true;
 }
 

@@ -9,6 +9,7 @@
 #include "vecops.h"
 #include "host_fp.h"
 #include "r1cs_batch.h"
+#include "nova_batch.h"
 
 using namespace kg;
 
@@ -83,10 +84,27 @@ __global__ void __launch_bounds__(256) k_vec_axpy(const uint64_t* a, Words8 s, c
   uint32_t wa[8], wb[8], wo[8];
   load_words(a, i, wa);
   load_words(b, i, wb);
-  // raw(b) * internal(s) stays in the ABI's Montgomery domain, like raw(a)
+  // raw(b) * internal(s) stays in the ABI's Montgomery domain, like raw(a)  (vecops.h axpy_step, written out)
   Fp<P> t = mul(limbs_from_words<P>(wb), from_ref<P>(s.w));
   words_from_limbs(reduce_2p(vred(norm(add(limbs_from_words<P>(wa), t)))), wo);
   store_words(out, i, wo);
+}
+// out_b = a_b + s_b * b_b for the vectors of a batch (kg_field_vec_axpy_batch): a lane per (vector, element) over the flattened index, so
+// that short vectors fill their waves and no grid dimension bounds the count; s_b is read from the device, one element per vector.
+// out may be a: every lane reads its own element before it writes it.
+template <class P>
+__global__ void __launch_bounds__(256) k_vec_axpy_batch(const uint64_t* a, size_t a_stride, const uint64_t* __restrict__ s, const uint64_t* __restrict__ b,
+                                                        size_t b_stride, uint64_t* out, size_t out_stride, size_t n, size_t first, size_t total) {
+  KG_SERVICE_PRIO();
+  const size_t t = first + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const AxpyBatchAt at = axpy_batch_at(t, n);
+  uint32_t wa[8], wb[8], ws[8], wo[8];
+  load_words(a, at.vec * a_stride + at.elem, wa);
+  load_words(b, at.vec * b_stride + at.elem, wb);
+  load_words(s, at.vec, ws);
+  words_from_limbs(reduce_2p(axpy_step(limbs_from_words<P>(wa), limbs_from_words<P>(wb), from_ref<P>(ws))), wo);
+  store_words(out, at.vec * out_stride + at.elem, wo);
 }
 
 // CSR sparse matrix-vector product (zkstd/src/matrix/row.rs:43-51, matrix.rs:36-48), G lanes per row: lanes stride over the
@@ -319,6 +337,38 @@ struct CrossOp : Csr3 {
       uint32_t wo[8];
       words_from_limbs(reduce_2p(r), wo);
       store_words(out, row, wo);
+    }
+    return false;
+  }
+};
+
+// kg_nova_cross_term_batch: the cross term for the pairs of one chunk of a batch against ONE shape -- the walker's kernels as they are over a
+// grid whose y index is the pair, as ProdBatchOp and CheckBatchOp run them: a lane per (short row, pair), a wave per (list entry, pair), the
+// work list built once by the y = 0 blocks of the launch that `lists`.  u1, u2: count elements each in the ABI form, scaled on the device
+// (u_factor: a representative of the single call's host-scaled value, and the row is canonicalised at the end, so T_b is the single call's
+// to the bit); null: us1, the host-scaled one.  Strides in elements.
+template <class P>
+struct CrossBatchOp : Csr3 {
+  static constexpr bool REPORTS = false;
+  const uint64_t *z1, *z2; size_t z1_stride, z2_stride; const uint64_t *u1, *u2; Limbs9 us1; uint64_t* out; size_t out_stride; bool lists;
+  __device__ __forceinline__ int klass(size_t row) const { return lists && blockIdx.y == 0 ? Csr3::klass(row) : 0; }
+  __device__ __forceinline__ Fp<P> factor(const uint64_t* u, size_t b) const {
+    if (u == nullptr) return Fp<P>::from_const(us1.l);
+    uint32_t wu[8];
+    load_words(u, b, wu);
+    return u_factor(limbs_from_words<P>(wu), Fp<P>::from_const(P::C_XT_U));
+  }
+  template <int G>
+  __device__ __forceinline__ bool row(size_t row, int lane) const {
+    if (G == 1 && Csr3::klass(row) != 0) return false;      // a list's row: not this lane's
+    const size_t b = blockIdx.y;
+    Fp<P> az[2], bz[2], cz[2];
+    dots<P, G, 2>(row, lane, z1 + b * z1_stride * 4, z2 + b * z2_stride * 4, az, bz, cz);
+    if (lane == 0) {
+      const Fp<P> r = cross_term_row(az[0], az[1], bz[0], bz[1], cz[0], cz[1], factor(u1, b), factor(u2, b), Fp<P>::from_const(P::C_XT_HAD));
+      uint32_t wo[8];
+      words_from_limbs(reduce_2p(r), wo);
+      store_words(out, b * out_stride + row, wo);
     }
     return false;
   }
@@ -582,6 +632,23 @@ int kg_field_vec_axpy(kg_ctx* c, int field, const uint64_t* a, const uint64_t* h
   return KG_OK;
 }
 
+int kg_field_vec_axpy_batch(kg_ctx* c, int field, const uint64_t* d_a, size_t a_stride, const uint64_t* d_s, const uint64_t* d_b, size_t b_stride,
+                            uint64_t* d_out, size_t out_stride, size_t n, size_t count) {
+  if (!axpy_batch_args_ok(c, field, d_a, a_stride, d_s, d_b, b_stride, d_out, out_stride, n, count)) return KG_ERR_BAD_ARG;
+  if (axpy_batch_empty(n, count)) return KG_OK;
+  KG_HIP(c, hipSetDevice(c->device));
+  const size_t total = n * count;                          // (below 2^59: count * stride * 32 fits a size_t and stride >= n)
+  by_field(field, [&](auto p) {
+    for (size_t first = 0; first < total; first += AXPY_BATCH_LAUNCH_MAX) {
+      const size_t lanes = total - first < AXPY_BATCH_LAUNCH_MAX ? total - first : AXPY_BATCH_LAUNCH_MAX;
+      hipLaunchKernelGGL(k_vec_axpy_batch<decltype(p)>, grid256(lanes), dim3(256), 0, c->stream, d_a, a_stride, d_s, d_b, b_stride, d_out, out_stride, n, first,
+                         total);
+    }
+  });
+  KG_HIP(c, hipGetLastError());
+  return KG_OK;
+}
+
 }  // extern "C"
 
 namespace kg {
@@ -657,6 +724,34 @@ int kg_nova_cross_term(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, c
   const RowWs ws(c->ws_vec.get(), m);
   KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, c->stream));
   by_field(field, [&](auto p) { launch_rows(c->stream, CrossOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z1, d_z2, u1, u2, d_out}, m, ws); });
+  KG_HIP(c, hipGetLastError());
+  return KG_OK;
+}
+
+// one shape against `count` pairs: a memset, then two launches per chunk of 65535 pairs, whatever count is; the first chunk's first launch
+// builds the work list, every later launch reads it.  Nothing is read back.
+int kg_nova_cross_term_batch(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z1, size_t z1_stride,
+                             const uint64_t* d_z2, size_t z2_stride, size_t count, const uint64_t* d_u1, const uint64_t* d_u2, uint64_t* d_out,
+                             size_t out_stride) {
+  if (!nova_cross_batch_args_ok(c, field, a, b, cm, m, d_z1, z1_stride, d_z2, z2_stride, count, d_out, out_stride)) return KG_ERR_BAD_ARG;
+  if (r1cs_batch_empty(m, count)) return KG_OK;
+  KG_HIP(c, hipSetDevice(c->device));
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  const RowWs ws(c->ws_vec.get(), m);
+  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, c->stream));
+  const bool fr = field == KG_FR;
+  const Limbs9 us1 = scaled(fr ? HostFrP::ONE : HostFqP::ONE, fr);
+  by_field(field, [&](auto p) {
+    using Op = CrossBatchOp<decltype(p)>;
+    for (size_t i = 0; i < r1cs_batch_chunks(count); ++i) {
+      const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
+      const Op op{{view(a), view(b), view(cm)}, d_z1 + ch.first * z1_stride * 4, d_z2 + ch.first * z2_stride * 4, z1_stride, z2_stride,
+                  d_u1 ? d_u1 + ch.first * 4 : nullptr, d_u2 ? d_u2 + ch.first * 4 : nullptr, us1, d_out + ch.first * out_stride * 4, out_stride, i == 0};
+      const unsigned y = (unsigned)ch.count;
+      hipLaunchKernelGGL(k_rows_lane<Op>, dim3(grid256(m).x, y), dim3(256), 0, c->stream, op, m, ws);
+      hipLaunchKernelGGL(k_rows_wave<Op>, dim3(r1cs_batch_grid_x(256, ch.count), y), dim3(256), 0, c->stream, op, ws.summary, ws.list, ws.count);
+    }
+  });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
 }

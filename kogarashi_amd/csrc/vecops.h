@@ -18,6 +18,13 @@ KG_HD F dot_step(const F& sum, const F& z_raw, const F& v_raw) { return vred(nor
 template <class F>
 KG_HD F dot_merge(const F& a, const F& b) { return vred(norm(add(a, b))); }
 
+// one element of a Nova fold (nova/src/relaxed_r1cs/witness.rs:56-70): a + s * b with a and b raw (the ABI words as limbs, any 256-bit
+// value) and s in internal form (from_ref of its ABI words: s * 2^261, below 2p): raw(b) * internal(s) stays in the ABI's Montgomery
+// domain, like raw(a).  One product, a lazy sum, one value reduction; the caller canonicalises (reduce_2p).  The batch's kernel (a scalar
+// per vector, read on the device) runs this body; the single call's k_vec_axpy has the same sequence written out.
+template <class F>
+KG_HD F axpy_step(const F& a_raw, const F& b_raw, const F& s) { return vred(norm(add(a_raw, mul(b_raw, s)))); }
+
 // Nova's cross term for one constraint row (nova/src/prover.rs:81-89):
 //   AZ1 * BZ2 + AZ2 * BZ1 - u1 * CZ2 - u2 * CZ1
 // az*, bz*, cz*: row sums as dot_step / dot_merge leave them (x * 2^251, below 1.06p).  u1s, u2s: u * 2^266 (the ABI form

@@ -37,6 +37,7 @@ EXPORTS = [
     "kg_groth16_prove_batch", "kg_groth16_prove_batch_plan",
     "kg_r1cs_prod_batch", "kg_groth16_prove_r1cs_batch",
     "kg_r1cs_check_batch", "kg_groth16_witness_check_batch",
+    "kg_nova_cross_term_batch", "kg_field_vec_axpy_batch", "kg_points_muladd_batch",
 ]
 
 
@@ -128,6 +129,15 @@ def load():
         _lib.kg_groth16_witness_check_batch.restype = C.c_int
         _lib.kg_groth16_witness_check_batch.argtypes = [C.c_void_p, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
                                                         C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        _lib.kg_nova_cross_term_batch.restype = C.c_int
+        _lib.kg_nova_cross_term_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(Csr), C.POINTER(Csr), C.POINTER(Csr), C.c_size_t, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        _lib.kg_field_vec_axpy_batch.restype = C.c_int
+        _lib.kg_field_vec_axpy_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                 C.c_size_t, C.c_size_t]
+        _lib.kg_points_muladd_batch.restype = C.c_int
+        _lib.kg_points_muladd_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                                C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -511,6 +521,29 @@ class Context:
                                                            _vp(x), C.c_size_t(x_stride), _vp(w), C.c_size_t(w_stride), C.c_size_t(count), _vp(status),
                                                            C.c_size_t(status_stride), _vp(summary.ptr)), "kg_groth16_witness_check_batch")
         return summary
+
+    def nova_cross_term_batch(self, field: int, a, b, c, m: int, z1: int, z1_stride: int, z2: int, z2_stride: int, count: int, u1: int, u2: int, out: int,
+                              out_stride: int):
+        """kg_nova_cross_term_batch: kg_nova_cross_term for count pairs against one shape.  Everything is a device pointer or a stride in
+        elements: pair b reads z1 at element b * z1_stride, z2 at element b * z2_stride and writes its m elements of T at element
+        b * out_stride of out; u1, u2: count elements each (0: one for every pair).  Enqueued on the context's stream."""
+        mk = lambda t: Csr(_vp(t[0]), _vp(t[1]), _vp(t[2]))
+        ca, cb, cc = mk(a), mk(b), mk(c)
+        self._chk(self._lib.kg_nova_cross_term_batch(self._h, int(field), C.byref(ca), C.byref(cb), C.byref(cc), C.c_size_t(m), _vp(z1), C.c_size_t(z1_stride),
+                                                     _vp(z2), C.c_size_t(z2_stride), C.c_size_t(count), _vp(u1), _vp(u2), _vp(out), C.c_size_t(out_stride)),
+                  "kg_nova_cross_term_batch")
+
+    def field_vec_axpy_batch(self, field: int, a: int, a_stride: int, s: int, b: int, b_stride: int, out: int, out_stride: int, n: int, count: int):
+        """kg_field_vec_axpy_batch: out_b = a_b + s_b * b_b for count vectors of n elements; s: count scalars on the DEVICE; strides in
+        elements; out may be a (same pointer, same stride).  Enqueued on the context's stream."""
+        self._chk(self._lib.kg_field_vec_axpy_batch(self._h, int(field), _vp(a), C.c_size_t(a_stride), _vp(s), _vp(b), C.c_size_t(b_stride), _vp(out),
+                                                    C.c_size_t(out_stride), C.c_size_t(n), C.c_size_t(count)), "kg_field_vec_axpy_batch")
+
+    def points_muladd_batch(self, curve: int, p_xy: int, p_inf: int, q_xy: int, q_inf: int, k: int, per_scalar: int, count: int, out_xy: int, out_inf: int):
+        """kg_points_muladd_batch: out_j = affine(P_j + k[j // per_scalar] * Q_j) for count points of G1 or Grumpkin, all device pointers
+        (p_inf, q_inf: 0 for no identities); out may be P.  Enqueued on the context's stream."""
+        self._chk(self._lib.kg_points_muladd_batch(self._h, int(curve), _vp(p_xy), _vp(p_inf), _vp(q_xy), _vp(q_inf), _vp(k), C.c_size_t(per_scalar),
+                                                   C.c_size_t(count), _vp(out_xy), _vp(out_inf)), "kg_points_muladd_batch")
 
     def fixed_base_mul(self, curve: int, k: int, n: int, out_xy: int, out_inf: int):
         self._chk(self._lib.kg_fixed_base_mul(self._h, curve, _vp(k), C.c_size_t(n), _vp(out_xy), _vp(out_inf)), "kg_fixed_base_mul")
