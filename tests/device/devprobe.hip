@@ -378,3 +378,6 @@ int dp_endo(int curve, const uint32_t* pts, uint32_t* o, size_t n) {
 }
 
 }  // extern "C"
+
+// the integer kernels of the long MSM's scalar side, one at a time (dp_sort_*, dp_task_*, dp_level_ops)
+#include "devprobe_sort.h"
