@@ -296,14 +296,13 @@ struct RowWs {
 };
 
 // ---- "how many items are bad, and which is the first": two words {count, lowest index} of type W in device memory -------------------
-// (kg_points_check: 64-bit words, n up to 2^37; kg_r1cs_check: 32-bit words inside RowWs, rows below 2^32).  k_summary_init sets them to
-// (0, n) on the stream before the kernels that fold into them -- and clears one more 32-bit word when given one (the check's long-row
-// counter) --, summary_read brings them back: it blocks.
+// (kg_points_check: 64-bit words, n up to 2^37; kg_r1cs_check: 32-bit words inside RowWs, rows below 2^32).  They are set to (0, n) on the
+// stream before the kernels that fold into them (k_summary_init; the R1CS checks: vec.hip k_check_batch_init, a pair per vector),
+// summary_read brings them back: it blocks.
 template <class W>
-static __global__ void k_summary_init(W* summary, W n, uint32_t* also_clear) {
+static __global__ void k_summary_init(W* summary, W n) {
   summary[0] = 0;
   summary[1] = n;
-  if (also_clear) *also_clear = 0;
 }
 // ONE lane speaks for n_bad items whose lowest index is `first`: one atomicAdd, one atomicMin
 template <class W>
@@ -424,13 +423,11 @@ struct MsmSorted {
   // real window count, an entry's index field is (window << merged_shift) | scalar index
   int merged_shift = 0, windows = 0;
 };
-// vec.hip: CSR matrix-vector product on a given queue; ws: a region of kg_ctx::ws_vec that nothing else uses meanwhile
+// vec.hip: CSR matrix-vector product on a given queue against `count` vectors: vector b at element b * z_stride of z, its m row sums at
+// element b * out_stride of out (kg_r1cs_prod_batch after its argument checks, kg_r1cs_prod with count = 1; the work list is built once per
+// call); ws: a region of kg_ctx::ws_vec that nothing else uses meanwhile
 int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
-                      const uint64_t* z, uint64_t* out, const RowWs& ws);
-// ... against `count` vectors: vector b at element b * z_stride of z, its m row sums at element b * out_stride of out (kg_r1cs_prod_batch
-// after its argument checks; the work list is built once per call)
-int r1cs_prod_batch_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
-                            const uint64_t* z, size_t z_stride, size_t count, uint64_t* out, size_t out_stride, const RowWs& ws);
+                      const uint64_t* z, size_t z_stride, size_t count, uint64_t* out, size_t out_stride, const RowWs& ws);
 // ntt.hip
 int ntt_prepare(kg_ctx* ctx, uint32_t log_n, int inverse);
 int ntt_enqueue(kg_ctx* ctx, hipStream_t st, uint64_t* tmp, uint64_t* d_data, uint32_t log_n, int inverse, int coset);

@@ -8,7 +8,7 @@
 // per proof, and a finishing lane per proof for A and C.  Everything is enqueued on the context's stream; nothing crosses to the host and
 // no worker thread is involved.  The number of launches does not depend on the group's size.
 // kg_groth16_prove_r1cs_batch is the same from the witnesses alone: the constraint matrices take the place of the evaluation vectors, the
-// fill kernel zeroes the rows and three batched CSR products (vec.hip: r1cs_prod_batch_enqueue) write A z, B z, C z straight into them.
+// fill kernel zeroes the rows and three batched CSR products (vec.hip: r1cs_prod_enqueue) write A z, B z, C z straight into them.
 #include "common.h"
 #include "groth16_qap.h"
 #include "groth16_batch.h"
@@ -182,8 +182,8 @@ int g16_batch_group_run(kg_ctx* ctx, const G16BatchCall& q, size_t first, size_t
       PhaseScope pe(ctx, "g16_batch_evaluate", st);
       uint64_t* rows[3] = {A, B, C};
       for (int v = 0; v < 3; ++v)
-        KG_TRY(r1cs_prod_batch_enqueue(ctx, st, KG_FR, q.mats[v]->d_row_ptr, q.mats[v]->d_col, q.mats[v]->d_val, m, Z, nz, g, rows[v], n,
-                                       RowWs(ctx->ws_vec.get(), m, v)));
+        KG_TRY(r1cs_prod_enqueue(ctx, st, KG_FR, q.mats[v]->d_row_ptr, q.mats[v]->d_col, q.mats[v]->d_val, m, Z, nz, g, rows[v], n,
+                                 RowWs(ctx->ws_vec.get(), m, v)));
       pe.end();
     }
   }

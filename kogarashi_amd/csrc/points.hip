@@ -62,7 +62,7 @@ int run_check(kg_ctx* c, int curve, const uint64_t* d_xy, const uint8_t* d_inf, 
   if (n >= ((size_t)1 << 37)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^37 points");       // the grid's x dimension
   KG_TRY(c->ws_points.ensure(DevMem{c, "point-check work space"}, WS_BYTES));
   unsigned long long* summary = c->ws_points.as<unsigned long long>();
-  hipLaunchKernelGGL(k_summary_init<unsigned long long>, dim3(1), dim3(1), 0, c->stream, summary, (unsigned long long)n, (uint32_t*)nullptr);
+  hipLaunchKernelGGL(k_summary_init<unsigned long long>, dim3(1), dim3(1), 0, c->stream, summary, (unsigned long long)n);
   const bool sub = (checks & KG_CHECK_SUBGROUP) != 0;
   if (curve == KG_G1) launch_check<Fq, false>(c, d_xy, d_inf, n, d_status, summary);
   else if (curve == KG_GRUMPKIN) launch_check<Fr, false>(c, d_xy, d_inf, n, d_status, summary);

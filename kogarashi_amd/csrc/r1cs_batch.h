@@ -17,6 +17,11 @@
 
 namespace kg {
 
+// The row classes of the sparse-row walker (vec.hip): a row of up to SHORT_ROW entries is summed by one lane, a longer one by a wave, one of
+// more than HUGE_ROW by a 1024-lane workgroup (the constant-one wire's row of a transposed system: an entry per constraint)
+constexpr uint32_t SHORT_ROW = 48;
+constexpr uint32_t HUGE_ROW = 4096;
+
 constexpr size_t R1CS_BATCH_GRID_Y_MAX = 65535;       // a HIP grid's y dimension carries at most 65535 blocks
 
 // number of launches' worth a batch of `count` vectors is cut into (0 for an empty batch); chunks run one after another on the stream
@@ -64,7 +69,7 @@ inline bool g16_r1cs_batch_args_ok(const void* ctx, const void* crs, size_t m, s
   return true;
 }
 
-// ---- the batched satisfiability check (kg_r1cs_check_batch, kg_groth16_witness_check_batch; vec.hip CheckBatchOp) -------------------------
+// ---- the batched satisfiability check (kg_r1cs_check_batch, kg_groth16_witness_check_batch; vec.hip CheckOp) -------------------------
 // Layout: vector b is read at element b * z_stride of d_z (or x_b at b * x_stride of d_x and w_b at b * w_stride of d_w), E_b at element
 // b * e_stride of d_e, u_b is element b of d_u; row i's status byte goes to d_status[b * status_stride + i] (a stride in BYTES) and the
 // vector's summary pair (bad rows, smallest bad row or m) to words 2 b and 2 b + 1 of d_summary.  The chunk rule is the product's.
@@ -115,7 +120,7 @@ inline bool g16_witness_check_batch_args_ok(const void* ctx, const Csr* a, const
   return true;
 }
 
-// ---- the batched Nova cross term (kg_nova_cross_term_batch; vec.hip CrossBatchOp) -------------------------------------------------------
+// ---- the batched Nova cross term (kg_nova_cross_term_batch; vec.hip CrossOp) -------------------------------------------------------
 // Layout: pair b reads z1_b at element b * z1_stride of d_z1 and z2_b at element b * z2_stride of d_z2 and writes the m elements of T_b at
 // element b * out_stride of d_out (out_stride >= m); u1_b and u2_b are element b of d_u1 / d_u2 (null: one for every pair -- not looked at
 // here).  The chunk rule is the product's.

@@ -219,7 +219,7 @@ int kg_groth16_setup_bn254(kg_ctx* ctx, const kg_csr* a, const kg_csr* b, const 
       hipLaunchKernelGGL(k_transpose_fill, dim3((unsigned)((nnz[j] + 255) / 256)), dim3(256), 0, st, mats[j]->d_row_ptr, mats[j]->d_col, mats[j]->d_val, m, nnz[j],
                          cursor, t_col, t_val);
     KG_HIP(ctx, hipGetLastError());
-    KG_TRY(r1cs_prod_enqueue(ctx, st, KG_FR, t_ptr, t_col, t_val, nv, pw, ev[j], RowWs(ctx->ws_vec.get(), nv)));
+    KG_TRY(r1cs_prod_enqueue(ctx, st, KG_FR, t_ptr, t_col, t_val, nv, pw, 0, 1, ev[j], nv, RowWs(ctx->ws_vec.get(), nv)));
   }
   if (nv) {
     // (beta * at + alpha * bt + ct) * inv, inv = 1/gamma for the l instance wires and 1/delta for the witness wires (zksnark.rs:180-187)

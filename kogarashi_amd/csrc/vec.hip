@@ -4,7 +4,6 @@
 // zkstd/src/arithmetic/limbs/bits_256/normal.rs:4-31,34-53,56-80,83-121,124-166,170-184,256-270 and the
 // point-wise polynomial ops groth16/src/poly.rs:168-195.  HBM-bound for add/sub/mul (96 B/element).
 #include <type_traits>
-#include <utility>
 #include "common.h"
 #include "vecops.h"
 #include "host_fp.h"
@@ -84,9 +83,8 @@ __global__ void __launch_bounds__(256) k_vec_axpy(const uint64_t* a, Words8 s, c
   uint32_t wa[8], wb[8], wo[8];
   load_words(a, i, wa);
   load_words(b, i, wb);
-  // raw(b) * internal(s) stays in the ABI's Montgomery domain, like raw(a)  (vecops.h axpy_step, written out)
-  Fp<P> t = mul(limbs_from_words<P>(wb), from_ref<P>(s.w));
-  words_from_limbs(reduce_2p(vred(norm(add(limbs_from_words<P>(wa), t)))), wo);
+  // raw(b) * internal(s) stays in the ABI's Montgomery domain, like raw(a)  (vecops.h axpy_step)
+  words_from_limbs(reduce_2p(axpy_step(limbs_from_words<P>(wa), limbs_from_words<P>(wb), from_ref<P>(s.w))), wo);
   store_words(out, i, wo);
 }
 // out_b = a_b + s_b * b_b for the vectors of a batch (kg_field_vec_axpy_batch): a lane per (vector, element) over the flattened index, so
@@ -160,67 +158,67 @@ __device__ __forceinline__ void row_dot(const uint64_t* __restrict__ row_ptr, co
 // transposed systems of the setup have one per heavily used wire, the constant-one wire touching every constraint -- would hold its whole
 // wave for ~0.5 us per term and z vector: it is put on a work list instead and gets a whole wave in the second launch (k_rows_wave).
 // What a row is and does comes from the operation Op:
-//   int klass(row)                       0: the lane takes the row; 1: the list's front (a wave); 2: the list's back (a workgroup: the product's
-//                                        k_r1cs_rows_huge)
-//   template <int G> bool row(row, lane) the row by G lanes -- G = 1: lane = 0; G = 64: every lane of the wave, lane 0 finishes; true (lane 0
-//                                        only): the row is bad
-//   REPORTS                              bad rows are folded into ws.summary: the lowest bad lane speaks for its 64 rows, a wave of
+//   int klass(row)                       0: a lane takes the row; 1: the list's front (a wave); 2: the list's back (a workgroup: the product's
+//                                        k_r1cs_rows_huge).  It depends on the matrix alone.
+//   template <int G> bool row(row, lane, b)   the row of vector b by G lanes -- G = 1: lane = 0; G = 64: every lane of the wave, lane 0 finishes;
+//                                        true (lane 0 only): the row is bad
+//   REPORTS, uint32_t* summary(b)        bad rows are folded into vector b's pair: the lowest bad lane speaks for its 64 rows, a wave of
 //                                        k_rows_wave for the rows it took (the list is in no particular order)
-//   uint32_t* summary()                  optional: the pair to fold into instead of ws.summary (the batched check: one per vector)
-constexpr uint32_t SHORT_ROW = 48;
-constexpr uint32_t HUGE_ROW = 4096;      // beyond: a 1024-lane workgroup per row (the constant-one wire's row of a transposed system: an entry per constraint)
+// One call runs the operation against `count` vectors (launch_rows): the vector is the block's y index b, and the single calls are the batch
+// of one.  A lane per (short row, vector), a wave per (list entry, vector).  The work list is the matrix's, so it is built once per call: by
+// the y = 0 blocks of the launch that `lists` (the first chunk's).  Every other lane that meets a long row leaves it to the list's launches;
+// trip counts stay wave-uniform, the list and its counters being the same for every y.
 struct CsrView {
   const uint64_t* row_ptr; const uint64_t* col; const uint64_t* val;
   __device__ __forceinline__ uint64_t len(size_t row) const { return row_ptr[row + 1] - row_ptr[row]; }
 };
-// Where a reporting operation's bad rows are folded: the work space's pair, unless the operation has a summary() of its own (the batched
-// check: a pair per vector, chosen by the block's y index)
-template <class Op, class = void>
-struct SummaryOf { static __device__ __forceinline__ uint32_t* of(const Op&, uint32_t* ws_summary) { return ws_summary; } };
 template <class Op>
-struct SummaryOf<Op, std::void_t<decltype(std::declval<const Op&>().summary())>> {
-  static __device__ __forceinline__ uint32_t* of(const Op& op, uint32_t*) { return op.summary(); }
-};
-template <class Op>
-__global__ void __launch_bounds__(256) k_rows_lane(Op op, size_t m, RowWs ws) {
+__global__ void __launch_bounds__(256) k_rows_lane(Op op, size_t m, RowWs ws, bool lists) {
   KG_SERVICE_PRIO();
-  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;                                       // lanes past the end and lanes whose row went to a work list report nothing
+  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  bool bad = false;                                       // lanes past the end and lanes whose row is a work list's report nothing
   if (row < m) {
     const int k = op.klass(row);
-    if (k == 2) ws.list[m - 1 - atomicAdd(ws.count + 1, 1u)] = (uint32_t)row;
-    else if (k == 1) ws.list[atomicAdd(ws.count, 1u)] = (uint32_t)row;
-    else bad = op.template row<1>(row, 0);
+    if (k == 0) bad = op.template row<1>(row, 0, b);
+    else if (lists && b == 0) {
+      if (k == 2) ws.list[m - 1 - atomicAdd(ws.count + 1, 1u)] = (uint32_t)row;
+      else ws.list[atomicAdd(ws.count, 1u)] = (uint32_t)row;
+    }
   }
-  if constexpr (Op::REPORTS) summary_fold(SummaryOf<Op>::of(op, ws.summary), bad, (uint32_t)row);
+  if constexpr (Op::REPORTS) summary_fold(op.summary(b), bad, (uint32_t)row);
 }
 // (the list as const __restrict__ parameters: handed over as a RowWs, the cross term's and the check's instances take one VGPR more)
 template <class Op>
-__global__ void __launch_bounds__(256) k_rows_wave(Op op, uint32_t* __restrict__ summary, const uint32_t* __restrict__ list, const uint32_t* __restrict__ count) {
+__global__ void __launch_bounds__(256) k_rows_wave(Op op, const uint32_t* __restrict__ list, const uint32_t* __restrict__ count) {
   KG_SERVICE_PRIO();
   const uint32_t nwaves = gridDim.x * (blockDim.x >> 6), wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
+  const size_t b = blockIdx.y;
   const uint32_t total = *count;
   uint32_t n_bad = 0, first = 0xffffffffu;                // lane 0 keeps them
   for (uint32_t i = wave; i < total; i += nwaves) {      // wave-uniform trip count: the shuffles inside row_dot see full waves
     const size_t row = list[i];
-    if (op.template row<64>(row, lane)) { ++n_bad; first = min(first, (uint32_t)row); }
+    if (op.template row<64>(row, lane, b)) { ++n_bad; first = min(first, (uint32_t)row); }
   }
   if constexpr (Op::REPORTS)
-    if (lane == 0 && n_bad != 0) summary_add(SummaryOf<Op>::of(op, summary), n_bad, first);
+    if (lane == 0 && n_bad != 0) summary_add(op.summary(b), n_bad, first);
 }
 
 // A HUGE row (more than HUGE_ROW entries) per WORKGROUP: 1024 lanes stride over its entries; wave sums by shuffles, the sixteen wave sums
 // through LDS.  Up to round 4 a wave took every long row: the transposed systems of the setup have a row per wire, and the constant-one wire's
 // row holds an entry per constraint -- 2^18 entries on 64 lanes took 4.8 ms of a 29 ms setup.  Rows of 49 .. 4096 entries (a range check's bit
 // sum: 254) keep a wave each: a circuit may hold tens of thousands of them, and 1024 waves take them in parallel.
+// A workgroup per (list entry, vector), the vector is the block's y index (strides in elements).
 constexpr int LONG_NT = 1024;
-// (the body of both huge-row kernels: the single product's and the batch's, which hands in its vector's z and out)
 template <class P>
-__device__ __forceinline__ void rows_huge(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col, const uint64_t* __restrict__ val,
-                                          const uint64_t* __restrict__ z, uint64_t* __restrict__ out, const uint32_t* __restrict__ long_rows,
-                                          const uint32_t* __restrict__ long_count, size_t m) {
+__global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
+                                                            const uint64_t* __restrict__ val, const uint64_t* __restrict__ z, size_t z_stride,
+                                                            uint64_t* __restrict__ out, size_t out_stride, const uint32_t* __restrict__ long_rows,
+                                                            const uint32_t* __restrict__ long_count, size_t m) {
+  KG_SERVICE_PRIO();
   __shared__ uint32_t part[LONG_NT / 64][9];
+  z += (size_t)blockIdx.y * z_stride * 4;
+  out += (size_t)blockIdx.y * out_stride * 4;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t total = long_count[1];
   for (uint32_t i = blockIdx.x; i < total; i += gridDim.x) {      // workgroup-uniform trip count
@@ -254,56 +252,25 @@ __device__ __forceinline__ void rows_huge(const uint64_t* __restrict__ row_ptr, 
     __syncthreads();
   }
 }
-template <class P>
-__global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
-                                                            const uint64_t* __restrict__ val, const uint64_t* __restrict__ z, uint64_t* __restrict__ out,
-                                                            const uint32_t* __restrict__ long_rows, const uint32_t* __restrict__ long_count, size_t m) {
-  KG_SERVICE_PRIO();
-  rows_huge<P>(row_ptr, col, val, z, out, long_rows, long_count, m);
-}
-// the batch's: a workgroup per (list entry, vector), the vector is the block's y index (strides in elements)
-template <class P>
-__global__ void __launch_bounds__(LONG_NT) k_r1cs_rows_huge_batch(const uint64_t* __restrict__ row_ptr, const uint64_t* __restrict__ col,
-                                                                  const uint64_t* __restrict__ val, const uint64_t* __restrict__ z, size_t z_stride,
-                                                                  uint64_t* __restrict__ out, size_t out_stride, const uint32_t* __restrict__ long_rows,
-                                                                  const uint32_t* __restrict__ long_count, size_t m) {
-  KG_SERVICE_PRIO();
-  rows_huge<P>(row_ptr, col, val, z + (size_t)blockIdx.y * z_stride * 4, out + (size_t)blockIdx.y * out_stride * 4, long_rows, long_count, m);
-}
 
-// out = M z  (zkstd/src/matrix/row.rs:43-51, matrix.rs:36-48): long rows to the list's front, huge rows to its back
+// out_b = M z_b  (zkstd/src/matrix/row.rs:43-51, matrix.rs:36-48): long rows to the list's front, huge rows to its back.  Vector b is read at
+// element b * z_stride of z, its row sums go to element b * out_stride of out.
 template <class P>
 struct ProdOp {
   static constexpr bool REPORTS = false;
-  CsrView M; const uint64_t* z; uint64_t* out;
+  CsrView M; const uint64_t* z; size_t z_stride; uint64_t* out; size_t out_stride;
   __device__ __forceinline__ int klass(size_t row) const { const uint64_t len = M.len(row); return len > HUGE_ROW ? 2 : (len > SHORT_ROW ? 1 : 0); }
   template <int G>
-  __device__ __forceinline__ bool row(size_t row, int lane) const {
+  __device__ __forceinline__ bool row(size_t row, int lane, size_t b) const {
+    const uint64_t* zb = z + b * z_stride * 4;
     Fp<P> sum[1];
-    row_dot<P, G, 1>(M.row_ptr, M.col, M.val, row, lane, z, z, sum);
+    row_dot<P, G, 1>(M.row_ptr, M.col, M.val, row, lane, zb, zb, sum);
     if (lane == 0) {
       uint32_t wo[8];
       words_from_limbs(reduce_2p(mul(sum[0], Fp<P>::from_const(P::C_FROM_REF))), wo);        // raw product domain -> the ABI's
-      store_words(out, row, wo);
+      store_words(out, b * out_stride + row, wo);
     }
     return false;
-  }
-};
-// out_b = M z_b for the vectors of one chunk of a batch (kg_r1cs_prod_batch): the walker's kernels as they are over a grid whose y index is
-// the vector -- a lane per (short row, vector), a wave per (list entry, vector).  A row's class depends on the matrix alone, so the work
-// list is built once: by the y = 0 blocks of the launch that `lists` (the batch's first chunk).  Every other lane that meets a long row
-// leaves it to the list's launches; trip counts stay wave-uniform, the list and its counters being the same for every y.
-template <class P>
-struct ProdBatchOp {
-  static constexpr bool REPORTS = false;
-  CsrView M; const uint64_t* z; uint64_t* out; size_t z_stride, out_stride; bool lists;      // strides in elements
-  __device__ __forceinline__ ProdOp<P> vec() const { return {M, z + (size_t)blockIdx.y * z_stride * 4, out + (size_t)blockIdx.y * out_stride * 4}; }
-  __device__ __forceinline__ int klass(size_t row) const { return lists && blockIdx.y == 0 ? vec().klass(row) : 0; }
-  template <int G>
-  __device__ __forceinline__ bool row(size_t row, int lane) const {
-    const ProdOp<P> v = vec();
-    if (G == 1 && v.klass(row) != 0) return false;          // a list's row: not this lane's
-    return v.template row<G>(row, lane);
   }
 };
 
@@ -319,53 +286,33 @@ struct Csr3 {
     row_dot<P, G, NZ>(C.row_ptr, C.col, C.val, row, lane, z1, z2, cz);
   }
 };
+// A u per vector in the factor form the row functions want next to raw row sums, u * 2^266: element b of `u` (the ABI form) scaled on the
+// device (u_factor), or, when the call has no such array, `us`: one value for every vector, scaled on the host (scaled()).  Both are
+// representatives of one residue and the row is canonicalised at the end, so the two ways give the same words.
+// DEV_U = false: the call has no arrays at all, and the kernel no load and no select (the single cross term's wave kernel keeps its time so).
 struct Limbs9 { uint32_t l[9]; };
+template <class P, bool DEV_U = true>
+__device__ __forceinline__ Fp<P> u_of(const uint64_t* u, const Limbs9& us, size_t b) {
+  if (!DEV_U || u == nullptr) return Fp<P>::from_const(us.l);
+  uint32_t wu[8];
+  load_words(u, b, wu);
+  return u_factor(limbs_from_words<P>(wu), Fp<P>::from_const(P::C_XT_U));
+}
 
 // Nova's cross term (nova/src/prover.rs:53-90): T = AZ1 o BZ2 + AZ2 o BZ1 - u1 * CZ2 - u2 * CZ1; bound by its ~12 products per row.
-// u1s, u2s: u * 2^266 as limbs (host-side), the factor form cross_term_row wants next to raw row sums.
-template <class P>
+// Pair b reads z1_b, z2_b at elements b * z1_stride, b * z2_stride and writes T_b at element b * out_stride.  kg_nova_cross_term hands in
+// its two host-scaled u and no arrays (DEV_U = false), kg_nova_cross_term_batch its arrays (each may be null: u = 1, the host-scaled one).
+template <class P, bool DEV_U>
 struct CrossOp : Csr3 {
   static constexpr bool REPORTS = false;
-  const uint64_t *z1, *z2; Limbs9 u1s, u2s; uint64_t* out;
+  const uint64_t* z1; size_t z1_stride; const uint64_t* z2; size_t z2_stride; const uint64_t *u1, *u2; Limbs9 us1, us2; uint64_t* out; size_t out_stride;
   template <int G>
-  __device__ __forceinline__ bool row(size_t row, int lane) const {
-    Fp<P> az[2], bz[2], cz[2];
-    dots<P, G, 2>(row, lane, z1, z2, az, bz, cz);
-    if (lane == 0) {
-      const Fp<P> r = cross_term_row(az[0], az[1], bz[0], bz[1], cz[0], cz[1], Fp<P>::from_const(u1s.l), Fp<P>::from_const(u2s.l),
-                                     Fp<P>::from_const(P::C_XT_HAD));
-      uint32_t wo[8];
-      words_from_limbs(reduce_2p(r), wo);
-      store_words(out, row, wo);
-    }
-    return false;
-  }
-};
-
-// kg_nova_cross_term_batch: the cross term for the pairs of one chunk of a batch against ONE shape -- the walker's kernels as they are over a
-// grid whose y index is the pair, as ProdBatchOp and CheckBatchOp run them: a lane per (short row, pair), a wave per (list entry, pair), the
-// work list built once by the y = 0 blocks of the launch that `lists`.  u1, u2: count elements each in the ABI form, scaled on the device
-// (u_factor: a representative of the single call's host-scaled value, and the row is canonicalised at the end, so T_b is the single call's
-// to the bit); null: us1, the host-scaled one.  Strides in elements.
-template <class P>
-struct CrossBatchOp : Csr3 {
-  static constexpr bool REPORTS = false;
-  const uint64_t *z1, *z2; size_t z1_stride, z2_stride; const uint64_t *u1, *u2; Limbs9 us1; uint64_t* out; size_t out_stride; bool lists;
-  __device__ __forceinline__ int klass(size_t row) const { return lists && blockIdx.y == 0 ? Csr3::klass(row) : 0; }
-  __device__ __forceinline__ Fp<P> factor(const uint64_t* u, size_t b) const {
-    if (u == nullptr) return Fp<P>::from_const(us1.l);
-    uint32_t wu[8];
-    load_words(u, b, wu);
-    return u_factor(limbs_from_words<P>(wu), Fp<P>::from_const(P::C_XT_U));
-  }
-  template <int G>
-  __device__ __forceinline__ bool row(size_t row, int lane) const {
-    if (G == 1 && Csr3::klass(row) != 0) return false;      // a list's row: not this lane's
-    const size_t b = blockIdx.y;
+  __device__ __forceinline__ bool row(size_t row, int lane, size_t b) const {
     Fp<P> az[2], bz[2], cz[2];
     dots<P, G, 2>(row, lane, z1 + b * z1_stride * 4, z2 + b * z2_stride * 4, az, bz, cz);
     if (lane == 0) {
-      const Fp<P> r = cross_term_row(az[0], az[1], bz[0], bz[1], cz[0], cz[1], factor(u1, b), factor(u2, b), Fp<P>::from_const(P::C_XT_HAD));
+      const Fp<P> r = cross_term_row(az[0], az[1], bz[0], bz[1], cz[0], cz[1], u_of<P, DEV_U>(u1, us1, b), u_of<P, DEV_U>(u2, us2, b),
+                                     Fp<P>::from_const(P::C_XT_HAD));
       uint32_t wo[8];
       words_from_limbs(reduce_2p(r), wo);
       store_words(out, b * out_stride + row, wo);
@@ -374,38 +321,13 @@ struct CrossBatchOp : Csr3 {
   }
 };
 
-// kg_r1cs_check: is (A z)_i (B z)_i = u (C z)_i + E_i for every row?  (nova/src/relaxed_r1cs.rs:81-114 is_sat_relaxed; u = 1 and E = 0:
-// zkstd/src/r1cs.rs:62-77 is_sat.)  The shape of the cross term with one z vector; instead of an element per row it leaves a status byte
-// (when asked) and the summary (common.h; row indices are below 2^32).
-// us: u * 2^266 as limbs (host-side, like the cross term's).  e == nullptr: E = 0, nothing is read.
-template <class P>
-struct CheckOp : Csr3 {
-  static constexpr bool REPORTS = true;
-  const uint64_t* z; Limbs9 us; const uint64_t* e; uint8_t* status;
-  template <int G>
-  __device__ __forceinline__ bool row(size_t row, int lane) const {
-    Fp<P> az[1], bz[1], cz[1];
-    dots<P, G, 1>(row, lane, z, z, az, bz, cz);
-    if (lane != 0) return false;
-    Fp<P> er = Fp<P>::zero();
-    if (e != nullptr) {
-      uint32_t we[8];
-      load_words(e, row, we);
-      er = limbs_from_words<P>(we);
-    }
-    const bool bad = !is_zero_mod_p(sat_residual_row(az[0], bz[0], cz[0], Fp<P>::from_const(us.l), er, Fp<P>::from_const(P::C_XT_HAD)));
-    if (status != nullptr) status[row] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
-    return bad;
-  }
-};
-
-// kg_r1cs_check_batch / kg_groth16_witness_check_batch: the check for the vectors of one chunk of a batch against ONE shape -- the walker's
-// kernels as they are over a grid whose y index is the vector, as ProdBatchOp runs them: a lane per (short row, vector), a wave per (list
-// entry, vector), the work list built once by the y = 0 blocks of the launch that `lists`.  Every vector folds into its own pair of `sums`
-// (summary(): SummaryOf hands it to the walker), so a lane of k_rows_lane speaks for its 64 rows of vector blockIdx.y and a wave of k_rows_wave
-// for the rows it took of that vector: at most one atomicAdd / atomicMin pair per wave and launch, spread over count addresses.
-// Z: the batch's vector source, vec(b) is what row_dot reads vector b through.  u: count elements in the ABI form, scaled on the device
-// (u_factor; null: us1, the host-scaled one of the single call).  Strides in elements, status_stride in bytes.
+// kg_r1cs_check, kg_r1cs_check_batch, kg_groth16_witness_check_batch: is (A z)_i (B z)_i = u (C z)_i + E_i for every row?
+// (nova/src/relaxed_r1cs.rs:81-114 is_sat_relaxed; u = 1 and E = 0: zkstd/src/r1cs.rs:62-77 is_sat.)  The shape of the cross term with one z
+// vector; instead of an element per row it leaves a status byte (when asked) and the vector's summary pair (common.h; row indices are
+// below 2^32).  Every vector folds into its own pair of `sums`, so a lane of k_rows_lane speaks for its 64 rows of vector b and a wave of
+// k_rows_wave for the rows it took of that vector: at most one atomicAdd / atomicMin pair per wave and launch, spread over count addresses.
+// Z: the vectors' source, vec(b) is what row_dot reads vector b through (the single call: ZStrided{d_z, 0}, and sums is the work space's
+// pair).  e == nullptr: E = 0, nothing is read.  Strides in elements, status_stride in bytes.
 struct ZStrided {
   const uint64_t* z; size_t stride;
   __device__ __forceinline__ const uint64_t* vec(size_t b) const { return z + b * stride * 4; }
@@ -417,35 +339,28 @@ struct ZSplitStrided {
   ZSplitStrided from(size_t first) const { return {x + first * x_stride * 4, x_stride, w + first * w_stride * 4, w_stride, l}; }
 };
 template <class P, class Z>
-struct CheckBatchOp : Csr3 {
+struct CheckOp : Csr3 {
   static constexpr bool REPORTS = true;
-  Z z; const uint64_t* u; Limbs9 us1; const uint64_t* e; size_t e_stride; uint8_t* status; size_t status_stride; uint32_t* sums; bool lists;
-  __device__ __forceinline__ uint32_t* summary() const { return sums + r1cs_check_batch_summary_word(blockIdx.y); }
-  __device__ __forceinline__ int klass(size_t row) const { return lists && blockIdx.y == 0 ? Csr3::klass(row) : 0; }
+  Z z; const uint64_t* u; Limbs9 us; const uint64_t* e; size_t e_stride; uint8_t* status; size_t status_stride; uint32_t* sums;
+  __device__ __forceinline__ uint32_t* summary(size_t b) const { return sums + r1cs_check_batch_summary_word(b); }
   template <int G>
-  __device__ __forceinline__ bool row(size_t row, int lane) const {
-    if (G == 1 && Csr3::klass(row) != 0) return false;      // a list's row: not this lane's
-    const size_t b = blockIdx.y;
+  __device__ __forceinline__ bool row(size_t row, int lane, size_t b) const {
     const auto zb = z.vec(b);
     Fp<P> az[1], bz[1], cz[1];
     dots<P, G, 1>(row, lane, zb, zb, az, bz, cz);
     if (lane != 0) return false;
-    Fp<P> us = Fp<P>::from_const(us1.l), er = Fp<P>::zero();
-    uint32_t wl[8];
-    if (u != nullptr) {
-      load_words(u, b, wl);
-      us = u_factor(limbs_from_words<P>(wl), Fp<P>::from_const(P::C_XT_U));
-    }
+    Fp<P> er = Fp<P>::zero();
     if (e != nullptr) {
-      load_words(e, b * e_stride + row, wl);
-      er = limbs_from_words<P>(wl);
+      uint32_t we[8];
+      load_words(e, b * e_stride + row, we);
+      er = limbs_from_words<P>(we);
     }
-    const bool bad = !is_zero_mod_p(sat_residual_row(az[0], bz[0], cz[0], us, er, Fp<P>::from_const(P::C_XT_HAD)));
+    const bool bad = !is_zero_mod_p(sat_residual_row(az[0], bz[0], cz[0], u_of<P>(u, us, b), er, Fp<P>::from_const(P::C_XT_HAD)));
     if (status != nullptr) status[r1cs_check_batch_status_byte(b, status_stride, row)] = bad ? (uint8_t)KG_ROW_UNSAT : (uint8_t)0;
     return bad;
   }
 };
-// the batch's one initialising launch: every vector's pair to (0, m), and the two list counters
+// the check's one initialising launch: every vector's pair to (0, m), and the two list counters
 __global__ void __launch_bounds__(256) k_check_batch_init(uint32_t* __restrict__ sums, size_t count, uint32_t m, uint32_t* __restrict__ counters) {
   const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b == 0 && counters != nullptr) { counters[0] = 0; counters[1] = 0; }      // (no rows: no list, no counters)
@@ -562,10 +477,25 @@ void by_field(int field, Fn&& fn) {
 }
 dim3 grid256(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
-template <class Op>
-void launch_rows(hipStream_t st, const Op& op, size_t m, const RowWs& ws) {
-  hipLaunchKernelGGL(k_rows_lane<Op>, grid256(m), dim3(256), 0, st, op, m, ws);
-  hipLaunchKernelGGL(k_rows_wave<Op>, dim3(256), dim3(256), 0, st, op, ws.summary, ws.list, ws.count);
+// One operation against `count` vectors (strides in elements, r1cs_batch.h), the counters of ws cleared on the stream before: two launches per
+// chunk of 65535 vectors, whatever count is -- for one vector grid256(m) blocks of lanes and 256 blocks of waves.  make_op(chunk): the
+// operation for the chunk's vectors, its pointers offset to the chunk's first; the first chunk's first launch builds the work list, every
+// later launch reads it.  then(chunk): what else the chunk needs (the product's huge rows).
+template <class MakeOp, class Then>
+void launch_rows(hipStream_t st, size_t m, size_t count, const RowWs& ws, MakeOp&& make_op, Then&& then) {
+  for (size_t i = 0; i < r1cs_batch_chunks(count); ++i) {
+    const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
+    const auto op = make_op(ch);
+    using Op = std::remove_const_t<decltype(op)>;
+    const unsigned y = (unsigned)ch.count;
+    hipLaunchKernelGGL(k_rows_lane<Op>, dim3(grid256(m).x, y), dim3(256), 0, st, op, m, ws, i == 0);
+    hipLaunchKernelGGL(k_rows_wave<Op>, dim3(r1cs_batch_grid_x(256, ch.count), y), dim3(256), 0, st, op, ws.list, ws.count);
+    then(ch);
+  }
+}
+template <class MakeOp>
+void launch_rows(hipStream_t st, size_t m, size_t count, const RowWs& ws, MakeOp&& make_op) {
+  launch_rows(st, m, count, ws, make_op, [](const R1csBatchChunk&) {});
 }
 CsrView view(const kg_csr* x) { return {x->d_row_ptr, x->d_col, x->d_val}; }
 // a, b, c all there, with all their arrays?
@@ -652,35 +582,20 @@ int kg_field_vec_axpy_batch(kg_ctx* c, int field, const uint64_t* d_a, size_t a_
 }  // extern "C"
 
 namespace kg {
-int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
-                      const uint64_t* z, uint64_t* out, const RowWs& ws) {
-  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, st));
-  by_field(field, [&](auto p) {
-    using P = decltype(p);
-    launch_rows(st, ProdOp<P>{{row_ptr, col, val}, z, out}, m, ws);
-    hipLaunchKernelGGL(k_r1cs_rows_huge<P>, dim3(64), dim3(LONG_NT), 0, st, row_ptr, col, val, z, out, ws.list, ws.count, m);
-  });
-  KG_HIP(c, hipGetLastError());
-  return KG_OK;
-}
 // one matrix against `count` vectors (strides in elements, r1cs_batch.h): a memset and three launches per chunk of 65535 vectors, whatever
 // count is; the first chunk's first launch builds the work list, every later launch reads it
-int r1cs_prod_batch_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
-                            const uint64_t* z, size_t z_stride, size_t count, uint64_t* out, size_t out_stride, const RowWs& ws) {
+int r1cs_prod_enqueue(kg_ctx* c, hipStream_t st, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m,
+                      const uint64_t* z, size_t z_stride, size_t count, uint64_t* out, size_t out_stride, const RowWs& ws) {
   KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, st));
   by_field(field, [&](auto p) {
     using P = decltype(p);
-    for (size_t i = 0; i < r1cs_batch_chunks(count); ++i) {
-      const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
-      const uint64_t* zc = z + ch.first * z_stride * 4;
-      uint64_t* oc = out + ch.first * out_stride * 4;
-      const ProdBatchOp<P> op{{row_ptr, col, val}, zc, oc, z_stride, out_stride, i == 0};
-      const unsigned y = (unsigned)ch.count;
-      hipLaunchKernelGGL(k_rows_lane<ProdBatchOp<P>>, dim3(grid256(m).x, y), dim3(256), 0, st, op, m, ws);
-      hipLaunchKernelGGL(k_rows_wave<ProdBatchOp<P>>, dim3(r1cs_batch_grid_x(256, ch.count), y), dim3(256), 0, st, op, ws.summary, ws.list, ws.count);
-      hipLaunchKernelGGL(k_r1cs_rows_huge_batch<P>, dim3(r1cs_batch_grid_x(64, ch.count), y), dim3(LONG_NT), 0, st, row_ptr, col, val, zc, z_stride, oc,
-                         out_stride, ws.list, ws.count, m);
-    }
+    launch_rows(
+        st, m, count, ws,
+        [&](const R1csBatchChunk& ch) { return ProdOp<P>{{row_ptr, col, val}, z + ch.first * z_stride * 4, z_stride, out + ch.first * out_stride * 4, out_stride}; },
+        [&](const R1csBatchChunk& ch) {
+          hipLaunchKernelGGL(k_r1cs_rows_huge<P>, dim3(r1cs_batch_grid_x(64, ch.count), (unsigned)ch.count), dim3(LONG_NT), 0, st, row_ptr, col, val,
+                             z + ch.first * z_stride * 4, z_stride, out + ch.first * out_stride * 4, out_stride, ws.list, ws.count, m);
+        });
   });
   KG_HIP(c, hipGetLastError());
   return KG_OK;
@@ -696,7 +611,7 @@ int kg_r1cs_prod(kg_ctx* c, int field, const uint64_t* row_ptr, const uint64_t* 
   KG_HIP(c, hipSetDevice(c->device));
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
   KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
-  return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, out, RowWs(c->ws_vec.get(), m));
+  return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, 0, 1, out, m, RowWs(c->ws_vec.get(), m));
 }
 
 int kg_r1cs_prod_batch(kg_ctx* c, int field, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z,
@@ -705,12 +620,69 @@ int kg_r1cs_prod_batch(kg_ctx* c, int field, const uint64_t* row_ptr, const uint
   if (r1cs_batch_empty(m, count)) return KG_OK;
   KG_HIP(c, hipSetDevice(c->device));
   KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
-  return kg::r1cs_prod_batch_enqueue(c, c->stream, field, row_ptr, col, val, m, z, z_stride, count, out, out_stride, RowWs(c->ws_vec.get(), m));
+  return kg::r1cs_prod_enqueue(c, c->stream, field, row_ptr, col, val, m, z, z_stride, count, out, out_stride, RowWs(c->ws_vec.get(), m));
 }
 
 int kg_r1cs_evaluate(kg_ctx* c, const uint64_t* row_ptr, const uint64_t* col, const uint64_t* val, size_t m, const uint64_t* z, uint64_t* out) {
   return kg_r1cs_prod(c, KG_FR, row_ptr, col, val, m, z, out);
 }
+
+}  // extern "C"
+
+namespace {
+// The cross term of one shape against `count` pairs, after the entry's argument checks: a memset, then two launches per chunk (launch_rows).
+// d_u1, d_u2: a u per pair on the device, or null: us1, us2, one for every pair (DEV_U = false: both null).  Nothing is read back.
+template <bool DEV_U>
+int cross_enqueue(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z1, size_t z1_stride,
+                  const uint64_t* d_z2, size_t z2_stride, size_t count, const uint64_t* d_u1, const uint64_t* d_u2, const Limbs9& us1, const Limbs9& us2,
+                  uint64_t* d_out, size_t out_stride) {
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  const RowWs ws(c->ws_vec.get(), m);
+  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, c->stream));
+  by_field(field, [&](auto p) {
+    launch_rows(c->stream, m, count, ws, [&](const R1csBatchChunk& ch) {
+      return CrossOp<decltype(p), DEV_U>{{view(a), view(b), view(cm)}, d_z1 + ch.first * z1_stride * 4, z1_stride, d_z2 + ch.first * z2_stride * 4, z2_stride,
+                                         d_u1 ? d_u1 + ch.first * 4 : nullptr, d_u2 ? d_u2 + ch.first * 4 : nullptr, us1, us2, d_out + ch.first * out_stride * 4, out_stride};
+    });
+  });
+  KG_HIP(c, hipGetLastError());
+  return KG_OK;
+}
+// The check of one shape against `count` vectors read through the source Z, after the entry's argument checks and with the work space there:
+// one initialising launch, then two launches per chunk (launch_rows).  d_u: a u per vector on the device, or null: `us`, one for every
+// vector.  Nothing is read back.
+template <class Z>
+int check_enqueue(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const RowWs& ws, const Z& z, size_t count,
+                  const uint64_t* d_u, const Limbs9& us, const uint64_t* d_e, size_t e_stride, uint8_t* d_status, size_t status_stride, uint32_t* d_summary) {
+  hipLaunchKernelGGL(k_check_batch_init, grid256(count), dim3(256), 0, c->stream, d_summary, count, (uint32_t)m, ws.count);
+  by_field(field, [&](auto p) {
+    launch_rows(c->stream, m, count, ws, [&](const R1csBatchChunk& ch) {
+      return CheckOp<decltype(p), Z>{{view(a), view(b), view(cm)}, z.from(ch.first), d_u ? d_u + ch.first * 4 : nullptr, us,
+                                     d_e ? d_e + ch.first * e_stride * 4 : nullptr, e_stride, d_status ? d_status + ch.first * status_stride : nullptr,
+                                     status_stride, d_summary + 2 * ch.first};
+    });
+  });
+  KG_HIP(c, hipGetLastError());
+  return KG_OK;
+}
+// u = 1 in the factor form, for the calls without a u of their own
+Limbs9 scaled_one(int field) { return scaled(field == KG_FR ? HostFrP::ONE : HostFqP::ONE, field == KG_FR); }
+// the two batched checks after their argument checks
+template <class Z>
+int check_batch_enqueue(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const Z& z, size_t count, const uint64_t* d_u,
+                        const uint64_t* d_e, size_t e_stride, uint8_t* d_status, size_t status_stride, uint32_t* d_summary) {
+  KG_HIP(c, hipSetDevice(c->device));
+  if (m == 0) {                                            // no row, no list: the pairs alone, (0, 0)
+    hipLaunchKernelGGL(k_check_batch_init, grid256(count), dim3(256), 0, c->stream, d_summary, count, 0u, (uint32_t*)nullptr);
+    KG_HIP(c, hipGetLastError());
+    return KG_OK;
+  }
+  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
+  return check_enqueue(c, field, a, b, cm, m, RowWs(c->ws_vec.get(), m), z, count, d_u, scaled_one(field), d_e, e_stride, d_status, status_stride, d_summary);
+}
+}  // namespace
+
+extern "C" {
 
 int kg_nova_cross_term(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z1,
                        const uint64_t* d_z2, const uint64_t* h_u1, const uint64_t* h_u2, uint64_t* d_out) {
@@ -720,40 +692,17 @@ int kg_nova_cross_term(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, c
   KG_HIP(c, hipSetDevice(c->device));
   const Limbs9 u1 = scaled(h_u1, field == KG_FR), u2 = scaled(h_u2, field == KG_FR);
   if (m >= ((size_t)1 << 32)) return set_err(c, KG_ERR_BAD_ARG, "more than 2^32 rows");
-  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
-  const RowWs ws(c->ws_vec.get(), m);
-  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, c->stream));
-  by_field(field, [&](auto p) { launch_rows(c->stream, CrossOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z1, d_z2, u1, u2, d_out}, m, ws); });
-  KG_HIP(c, hipGetLastError());
-  return KG_OK;
+  return cross_enqueue<false>(c, field, a, b, cm, m, d_z1, 0, d_z2, 0, 1, nullptr, nullptr, u1, u2, d_out, m);
 }
 
-// one shape against `count` pairs: a memset, then two launches per chunk of 65535 pairs, whatever count is; the first chunk's first launch
-// builds the work list, every later launch reads it.  Nothing is read back.
 int kg_nova_cross_term_batch(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z1, size_t z1_stride,
                              const uint64_t* d_z2, size_t z2_stride, size_t count, const uint64_t* d_u1, const uint64_t* d_u2, uint64_t* d_out,
                              size_t out_stride) {
   if (!nova_cross_batch_args_ok(c, field, a, b, cm, m, d_z1, z1_stride, d_z2, z2_stride, count, d_out, out_stride)) return KG_ERR_BAD_ARG;
   if (r1cs_batch_empty(m, count)) return KG_OK;
   KG_HIP(c, hipSetDevice(c->device));
-  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
-  const RowWs ws(c->ws_vec.get(), m);
-  KG_HIP(c, hipMemsetAsync(ws.count, 0, 8, c->stream));
-  const bool fr = field == KG_FR;
-  const Limbs9 us1 = scaled(fr ? HostFrP::ONE : HostFqP::ONE, fr);
-  by_field(field, [&](auto p) {
-    using Op = CrossBatchOp<decltype(p)>;
-    for (size_t i = 0; i < r1cs_batch_chunks(count); ++i) {
-      const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
-      const Op op{{view(a), view(b), view(cm)}, d_z1 + ch.first * z1_stride * 4, d_z2 + ch.first * z2_stride * 4, z1_stride, z2_stride,
-                  d_u1 ? d_u1 + ch.first * 4 : nullptr, d_u2 ? d_u2 + ch.first * 4 : nullptr, us1, d_out + ch.first * out_stride * 4, out_stride, i == 0};
-      const unsigned y = (unsigned)ch.count;
-      hipLaunchKernelGGL(k_rows_lane<Op>, dim3(grid256(m).x, y), dim3(256), 0, c->stream, op, m, ws);
-      hipLaunchKernelGGL(k_rows_wave<Op>, dim3(r1cs_batch_grid_x(256, ch.count), y), dim3(256), 0, c->stream, op, ws.summary, ws.list, ws.count);
-    }
-  });
-  KG_HIP(c, hipGetLastError());
-  return KG_OK;
+  const Limbs9 one = scaled_one(field);
+  return cross_enqueue<true>(c, field, a, b, cm, m, d_z1, z1_stride, d_z2, z2_stride, count, d_u1, d_u2, one, one, d_out, out_stride);
 }
 
 int kg_r1cs_check(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z, const uint64_t* h_u,
@@ -767,52 +716,12 @@ int kg_r1cs_check(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const 
   }
   if (!d_z || !csr3_ok(a, b, cm)) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
-  const bool fr = field == KG_FR;
-  const Limbs9 us = scaled(h_u ? h_u : (fr ? HostFrP::ONE : HostFqP::ONE), fr);       // no u: the plain relation, u = 1
+  const Limbs9 us = h_u ? scaled(h_u, field == KG_FR) : scaled_one(field);       // no u: the plain relation, u = 1
   KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
   const RowWs ws(c->ws_vec.get(), m);
-  hipLaunchKernelGGL(k_summary_init<uint32_t>, dim3(1), dim3(1), 0, c->stream, ws.summary, (uint32_t)m, ws.count);
-  by_field(field, [&](auto p) { launch_rows(c->stream, CheckOp<decltype(p)>{{view(a), view(b), view(cm)}, d_z, us, d_e, d_status}, m, ws); });
-  KG_HIP(c, hipGetLastError());
+  KG_TRY(check_enqueue(c, field, a, b, cm, m, ws, ZStrided{d_z, 0}, 1, nullptr, us, d_e, 0, d_status, 0, ws.summary));
   return summary_read(c, ws.summary, out_bad, out_first_bad);
 }
-
-}  // extern "C"
-
-namespace {
-// one shape against `count` vectors read through the source Z (arguments checked by the callers): one initialising launch, then two launches per
-// chunk of 65535 vectors, whatever count is; the first chunk's first launch builds the work list, every later launch reads it.  Nothing is read back.
-template <class Z>
-int check_batch_enqueue(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const Z& z, size_t count, const uint64_t* d_u,
-                        const uint64_t* d_e, size_t e_stride, uint8_t* d_status, size_t status_stride, uint32_t* d_summary) {
-  KG_HIP(c, hipSetDevice(c->device));
-  if (m == 0) {                                            // no row, no list: the pairs alone, (0, 0)
-    hipLaunchKernelGGL(k_check_batch_init, grid256(count), dim3(256), 0, c->stream, d_summary, count, 0u, (uint32_t*)nullptr);
-    KG_HIP(c, hipGetLastError());
-    return KG_OK;
-  }
-  KG_TRY(c->ws_vec.ensure(DevMem{c, "workspace allocation"}, RowWs::bytes(m)));
-  const RowWs ws(c->ws_vec.get(), m);
-  hipLaunchKernelGGL(k_check_batch_init, grid256(count), dim3(256), 0, c->stream, d_summary, count, (uint32_t)m, ws.count);
-  const bool fr = field == KG_FR;
-  const Limbs9 us1 = scaled(fr ? HostFrP::ONE : HostFqP::ONE, fr);
-  by_field(field, [&](auto p) {
-    using Op = CheckBatchOp<decltype(p), Z>;
-    for (size_t i = 0; i < r1cs_batch_chunks(count); ++i) {
-      const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
-      const Op op{{view(a), view(b), view(cm)}, z.from(ch.first), d_u ? d_u + ch.first * 4 : nullptr, us1, d_e ? d_e + ch.first * e_stride * 4 : nullptr, e_stride,
-                  d_status ? d_status + ch.first * status_stride : nullptr, status_stride, d_summary + 2 * ch.first, i == 0};
-      const unsigned y = (unsigned)ch.count;
-      hipLaunchKernelGGL(k_rows_lane<Op>, dim3(grid256(m).x, y), dim3(256), 0, c->stream, op, m, ws);
-      hipLaunchKernelGGL(k_rows_wave<Op>, dim3(r1cs_batch_grid_x(256, ch.count), y), dim3(256), 0, c->stream, op, ws.summary, ws.list, ws.count);
-    }
-  });
-  KG_HIP(c, hipGetLastError());
-  return KG_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int kg_r1cs_check_batch(kg_ctx* c, int field, const kg_csr* a, const kg_csr* b, const kg_csr* cm, size_t m, const uint64_t* d_z, size_t z_stride, size_t count,
                         const uint64_t* d_u, const uint64_t* d_e, size_t e_stride, uint8_t* d_status, size_t status_stride, uint32_t* d_summary) {

@@ -20,8 +20,8 @@ KG_HD F dot_merge(const F& a, const F& b) { return vred(norm(add(a, b))); }
 
 // one element of a Nova fold (nova/src/relaxed_r1cs/witness.rs:56-70): a + s * b with a and b raw (the ABI words as limbs, any 256-bit
 // value) and s in internal form (from_ref of its ABI words: s * 2^261, below 2p): raw(b) * internal(s) stays in the ABI's Montgomery
-// domain, like raw(a).  One product, a lazy sum, one value reduction; the caller canonicalises (reduce_2p).  The batch's kernel (a scalar
-// per vector, read on the device) runs this body; the single call's k_vec_axpy has the same sequence written out.
+// domain, like raw(a).  One product, a lazy sum, one value reduction; the caller canonicalises (reduce_2p).  Both axpy kernels run this body: the single
+// call's (a scalar by value) and the batch's (a scalar per vector, read on the device).
 template <class F>
 KG_HD F axpy_step(const F& a_raw, const F& b_raw, const F& s) { return vred(norm(add(a_raw, mul(b_raw, s)))); }
 

@@ -1,4 +1,4 @@
-// r1cs_check_batch_host.cpp -- the parts of kg_r1cs_check_batch / kg_groth16_witness_check_batch (kogarashi_amd/csrc/vec.hip CheckBatchOp) that
+// r1cs_check_batch_host.cpp -- the parts of kg_r1cs_check_batch / kg_groth16_witness_check_batch (kogarashi_amd/csrc/vec.hip CheckOp) that
 // need no device, as a stand-alone program: tests/test_r1cs_check_batch_host.py builds it with g++, plain and with -fsanitize=address,undefined,
 // and runs it.
 //
@@ -11,7 +11,7 @@
 //           sat_residual_row, which aborts if it is not the factor form that function accepts
 //   split   r1cs_split_at: column j of x || w at j in {0, l - 1, l, l + m_l_1 - 1}, with l = 1 and with m_l_1 = 0
 //   fold    the walker's reporting over a simulated grid -- a lane per (row, vector) folded per wave as summary_fold does, the chunk rule
-//           and the pointer offsets check_batch_enqueue applies per chunk: vector b's pair and bytes depend on vector b's rows only, the bytes
+//           and the pointer offsets check_enqueue applies per chunk: vector b's pair and bytes depend on vector b's rows only, the bytes
 //           between two vectors' rows stay untouched
 #include <cstdio>
 #include <cstring>
@@ -198,7 +198,7 @@ static void simulate(size_t m, size_t count, size_t status_stride) {
     const R1csBatchChunk ch = r1cs_batch_chunk(count, i);
     EXPECT(ch.first == covered && ch.count >= 1 && ch.count <= R1CS_BATCH_GRID_Y_MAX);
     covered += ch.count;
-    uint32_t* chunk_sums = sums.data() + 2 * ch.first;                                        // the offsets check_batch_enqueue applies
+    uint32_t* chunk_sums = sums.data() + 2 * ch.first;                                        // the offsets check_enqueue applies
     uint8_t* chunk_status = status.data() + ch.first * status_stride;
     for (size_t y = 0; y < ch.count; ++y)                                                     // the grid's y
       for (size_t w0 = 0; w0 < m; w0 += 64) {                                                 // a wave of k_rows_lane: 64 rows of vector y

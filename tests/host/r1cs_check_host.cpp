@@ -17,6 +17,7 @@
 #include "../../kogarashi_amd/csrc/fp29.h"
 #include "../../kogarashi_amd/csrc/vecops.h"
 #include "../../kogarashi_amd/csrc/host_fp.h"
+#include "../../kogarashi_amd/csrc/r1cs_batch.h"      // SHORT_ROW
 
 using namespace kg;
 
@@ -27,7 +28,6 @@ template <class P> struct RawIn<Fp<P>> { static Fp<P> in(const uint32_t* w) { re
 template <class P> struct RawIn<FpChecked<P>> { static FpChecked<P> in(const uint32_t* w) { return FpChecked<P>::wrap(limbs_from_words<P>(w), 5.4); } };   // any 256-bit input
 #endif
 
-constexpr uint64_t SHORT_ROW = 48;          // vec.hip
 
 struct Csr { std::vector<uint64_t> rp, col, val; };
 

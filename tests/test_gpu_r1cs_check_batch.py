@@ -159,6 +159,42 @@ def test_stream_order(ctx, oracle, resident):
     assert ctx.worker_threads() == threads
 
 
+@pytest.mark.parametrize("fd", [0, 1])
+def test_single_and_batched_calls_share_one_work_space(ctx, oracle, resident, fd):
+    """One context, m = 300, nothing synchronised in between: a single check, a batched check of 3, a single cross term, a batched product of
+    2, a single product and a single check once more.  They share the launcher, the initialiser and the work space (the list, its two counters
+    and the single check's summary pair; the product alone has a list's back, row 61 of matrix B), so each call must rebuild what it uses.
+    Every word is compared with the oracle or with Python integers."""
+    O = oracle
+    sh, vecs = BC.case300(O, fd)
+    ptrs, m, n = resident(sh), sh.m, sh.nvars
+    first, last = vecs[1], vecs[4]                                                  # bad at perturbed_rows(m); the same z, plain, at the end
+    batch = Call(ctx, ptrs, sh, [vecs[0], vecs[2], vecs[4]])
+    dz, de = ctx.upload(first.z), ctx.upload(RC.to_mont(first.e, sh.p))
+    d_st = ctx.upload(np.full(m, 0xAA, dtype=np.uint8))
+    u1, u2 = vecs[0].u, vecs[5].u                                                   # random, p - 1
+    dz1, dz2, d_t = ctx.upload(vecs[2].z), ctx.upload(vecs[3].z), ctx.upload(np.zeros((m, 4), dtype=np.uint64))
+    zb = np.stack([vecs[3].z, last.z])
+    dzb, d_pb, d_p = ctx.upload(zb), ctx.upload(np.zeros((2, m, 4), dtype=np.uint64)), ctx.upload(np.zeros((m, 4), dtype=np.uint64))
+    assert sh.row_lengths()[1, RC.HUGE_ROW] == 5000
+    ctx.sync()
+    got_first = ctx.r1cs_check(fd, *ptrs, m, dz.ptr, first.u, de.ptr, d_st.ptr)     # (blocks, by its nature: the pair comes back)
+    batch.enqueue()
+    ctx.nova_cross_term(fd, *ptrs, m, dz1.ptr, dz2.ptr, u1, u2, d_t.ptr)
+    ctx.r1cs_prod_batch(fd, *ptrs[1], m, dzb.ptr, n, 2, d_pb.ptr, m)
+    ctx.r1cs_prod(fd, *ptrs[1], m, dz.ptr, d_p.ptr)
+    got_last = ctx.r1cs_check(fd, *ptrs, m, dzb.ptr + 32 * n)
+    ctx.sync()
+    want = first.want(sh)
+    assert got_first == want[1:] and want[1] == len(RC.perturbed_rows(m)) and (d_st.numpy() == want[0]).all()
+    batch.assert_matches(singles=False)
+    assert (d_t.numpy() == O.nova_cross_term(fd, *sh.mats, vecs[2].z, vecs[3].z, u1, u2)).all()
+    for b in range(2):
+        assert (d_pb.numpy()[b] == O.matrix_prod(fd, sh.mats[1], zb[b])).all(), b
+    assert (d_p.numpy() == O.matrix_prod(fd, sh.mats[1], first.z)).all()
+    assert got_last == last.want(sh, plain=True)[1:] and got_last != got_first
+
+
 def test_status_codes(ctx, oracle, resident):
     """KG_ERR_BAD_ARG before anything is dereferenced or enqueued -- the pointers of the refused calls are poisoned --, the outputs untouched;
     count == 0 enqueues nothing; m == 0 writes (0, 0) into count pairs and nothing else"""
