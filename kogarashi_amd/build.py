@@ -66,9 +66,10 @@ DEVPROBE_OUT = os.path.join(DEVPROBE_DIR, "libdevprobe.so")
 
 
 def devprobe_deps() -> list[str]:
-    """what libdevprobe.so is made from: its source and the sort entries it includes, the shared cases and every header under csrc/"""
+    """what libdevprobe.so is made from: its source and the sort and reduction entries it includes, the shared cases and every header under csrc/"""
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith((".h", ".inc"))]
-    return [DEVPROBE_SRC, os.path.join(DEVPROBE_DIR, "devprobe_sort.h"), os.path.join(os.path.dirname(DEVPROBE_DIR), "host", "arith_cases.h")] + headers
+    return [DEVPROBE_SRC, os.path.join(DEVPROBE_DIR, "devprobe_sort.h"), os.path.join(DEVPROBE_DIR, "devprobe_reduce.h"),
+            os.path.join(os.path.dirname(DEVPROBE_DIR), "host", "arith_cases.h")] + headers
 
 
 def build_devprobe(force: bool = False) -> str:

@@ -381,3 +381,5 @@ int dp_endo(int curve, const uint32_t* pts, uint32_t* o, size_t n) {
 
 // the integer kernels of the long MSM's scalar side, one at a time (dp_sort_*, dp_task_*, dp_level_ops)
 #include "devprobe_sort.h"
+// the point-side kernels of the long MSM, one at a time (dp_bases_*, dp_acc_tasks, dp_gather, dp_sum_tasks, dp_halve, dp_reduce_tail, dp_hot)
+#include "devprobe_reduce.h"

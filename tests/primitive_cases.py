@@ -1274,4 +1274,6 @@ DEV_EXPORTS = ["dp_raw_ops", "dp_raw2_ops", "dp_field_ops", "dp_curve_ops", "dp_
                "dp_endo", "dp_fp2s_raw_ops", "dp_fp2s_curve_ops",
                # the sort and task kernels of the long MSM, one at a time (tests/device/devprobe_sort.h, tests/sort_cases.py)
                "dp_sort_prep", "dp_sort_onepass", "dp_sort_zero_fill", "dp_sort_group_scan", "dp_sort_merge_groups", "dp_sort_group_scatter_big",
-               "dp_sort_fine_local", "dp_sort_fine_scatter", "dp_task_bucket_tables", "dp_task_bases", "dp_task_len_scatter", "dp_level_ops"]
+               "dp_sort_fine_local", "dp_sort_fine_scatter", "dp_task_bucket_tables", "dp_task_bases", "dp_task_len_scatter", "dp_level_ops",
+               # the point-side kernels of the long MSM, one at a time (tests/device/devprobe_reduce.h, tests/reduce_cases.py)
+               "dp_bases_prep", "dp_bases_table_next", "dp_acc_tasks", "dp_gather", "dp_sum_tasks", "dp_halve", "dp_reduce_tail", "dp_hot"]
