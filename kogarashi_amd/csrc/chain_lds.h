@@ -1,6 +1,6 @@
 // chain_lds.h -- what the one-lane 255-step chain kernels share (groth16_batch.hip: the assembly of a batch of proofs; points_fold.hip:
-// P + k Q for a batch of Nova folds): the chain's three operands in LDS columns, the loaders of an affine ABI point and the writer of an
-// affine result.  The chain itself is g16_mul2_ops (groth16_assemble.h).  Device code: include after common.h.
+// P + k Q for a batch of Nova folds): the chain's three operands in LDS columns and the loaders of an affine ABI point (the writer of
+// the affine result is common.h's put_affine_abi).  The chain itself is g16_mul2_ops (groth16_assemble.h).  Device code: include after common.h.
 #pragma once
 #include "common.h"
 #include "groth16_assemble.h"
@@ -28,28 +28,6 @@ __device__ __forceinline__ XYZZ<Fq> g16_g1_point(const uint32_t w[16], bool inf)
 __device__ __forceinline__ XYZZ<Fq2> g16_g2_point(const uint32_t w[32], bool inf) {
   if (inf) return XYZZ<Fq2>::identity();
   return from_affine(Affine<Fq2>{{from_ref<FqParams>(w), from_ref<FqParams>(w + 8)}, {from_ref<FqParams>(w + 16), from_ref<FqParams>(w + 24)}});
-}
-template <class P>
-__device__ __forceinline__ void g16_put(const Fp<P>& a, uint64_t* dst) {
-  uint32_t w[8];
-  to_ref(a, w);
-  store_words(dst, 0, w);
-}
-template <class G>
-__device__ __forceinline__ void g16_put(const Fp2<G>& a, uint64_t* dst) { g16_put(a.c0, dst); g16_put(a.c1, dst + 4); }
-// XYZZ -> affine ABI words and flag; the identity is (0, 1) + flag 1, as kg_fixed_base_mul writes it
-template <class F, int E64>
-__device__ __forceinline__ void g16_put_affine(const XYZZ<F>& p, uint64_t* dst, uint8_t* inf) {
-  Affine<F> a;
-  if (to_affine(p, a)) {
-    g16_put(a.x, dst);
-    g16_put(a.y, dst + E64);
-    *inf = 0;
-  } else {
-    g16_put(F::zero(), dst);
-    g16_put(F::one(), dst + E64);
-    *inf = 1;
-  }
 }
 
 }  // namespace kg

@@ -15,6 +15,7 @@
 #include <initializer_list>
 #include "../../include/kogarashi_amd.h"
 #include "curve.h"
+#include "curve_layout.h"
 #include "tuning.h"
 #include "worker_pool.h"
 #include "grow_buf.h"
@@ -209,6 +210,18 @@ struct JoinGuard {
     if (s__ != KG_OK) return s__; \
   } while (0)
 
+// Raises the dynamic-LDS limit of the kernels to `bytes`, once per device and instantiation (the attribute belongs to the function on a
+// device; the kernels are template arguments, so every set of them has a flag word of its own).  A load and a test on the launch path.
+template <auto... Kernels>
+inline int lds_attr_once(kg_ctx* ctx, int bytes) {
+  static std::atomic<uint64_t> attr_devs{0};
+  const uint64_t bit = (uint64_t)1 << (ctx->device & 63);
+  if (attr_devs.load() & bit) return KG_OK;
+  for (const void* k : {(const void*)Kernels...}) KG_HIP(ctx, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  attr_devs |= bit;
+  return KG_OK;
+}
+
 // hipMalloc for the library's own work spaces: when the device refuses, the blocks kg_free has kept are released and the request is
 // repeated once (the pool must never be what makes a call fail)
 hipError_t dev_alloc(kg_ctx* c, void** p, size_t bytes);
@@ -236,7 +249,7 @@ inline int PinMem::alloc(void** p, size_t bytes) {
 // (The flags were baked in at registration: the resident copy serves a call only when the call's flag array is the registered one at
 // the same offset, or both are absent; any other combination converts per call.)
 inline bool covers(const kg_ctx::Registered& r, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t n, size_t* off) {
-  const size_t pw64 = curve == KG_G2 ? 16 : 8;             // u64 words per ABI point
+  const size_t pw64 = affine_words64(curve);               // u64 words per ABI point
   if (r.curve != curve || d_bases < r.base) return false;
   const size_t off64 = (size_t)(d_bases - r.base);
   if (off64 % pw64 != 0 || off64 / pw64 + n > r.n) return false;
@@ -389,11 +402,37 @@ template <class P> struct RefIO<Fp<P>> {
     load_words(p, 0, w);
     return from_ref<P>(w);
   }
+  static __device__ __forceinline__ void store(const Fp<P>& a, uint64_t* p) {
+    uint32_t w[8];
+    to_ref(a, w);
+    store_words(p, 0, w);
+  }
 };
 template <class F> struct RefIO<Fp2<F>> {
   static constexpr int W64 = 8;
   static __device__ __forceinline__ Fp2<F> load(const uint64_t* p) { return {RefIO<F>::load(p), RefIO<F>::load(p + 4)}; }
+  static __device__ __forceinline__ void store(const Fp2<F>& a, uint64_t* p) { RefIO<F>::store(a.c0, p); RefIO<F>::store(a.c1, p + 4); }
 };
+// An affine result -> ABI words x | y and its flag; the identity is (0, 1) + flag 1 (macros/curve/weierstrass/group.rs:22-26).  Every kernel
+// that hands a point to the caller writes it here: from XYZZ (one inversion), or -- a kernel that inverts in batches -- already affine.
+template <class F>
+__device__ __forceinline__ void put_identity_abi(uint64_t* xy, uint8_t* inf) {
+  RefIO<F>::store(F::zero(), xy);
+  RefIO<F>::store(F::one(), xy + RefIO<F>::W64);
+  *inf = 1;
+}
+template <class F>
+__device__ __forceinline__ void put_affine_abi(const Affine<F>& a, uint64_t* xy, uint8_t* inf) {
+  RefIO<F>::store(a.x, xy);
+  RefIO<F>::store(a.y, xy + RefIO<F>::W64);
+  *inf = 0;
+}
+template <class F>
+__device__ __forceinline__ void put_affine_abi(const XYZZ<F>& p, uint64_t* xy, uint8_t* inf) {
+  Affine<F> a;
+  if (to_affine(p, a)) put_affine_abi(a, xy, inf);
+  else put_identity_abi<F>(xy, inf);
+}
 
 
 // msm.hip: scalar-side / base-side / host halves of an MSM (used by kg_msm and by the Groth16 prover).

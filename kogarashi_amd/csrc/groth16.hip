@@ -6,11 +6,10 @@
 // assembly (:71-98).  The polynomial vectors never leave HBM between steps; only the eight MSM results and the
 // three proof points touch the host, which also runs the six short scalar multiplications of the assembly
 // (sequential double-and-add, as in the reference).
-#include "common.h"
-#include "msm_internal.h"
+#include "msm_common.h"
 #include <chrono>
 #include <cstdlib>
-#include "host_fp.h"
+#include "host_point.h"
 #include "groth16_qap.h"
 #include <future>
 #include <vector>
@@ -45,15 +44,6 @@ template <> struct Gen<Fq2> {                   // bn254/src/params.rs:15-42 (ca
   }
 };
 
-template <class P>
-__device__ __forceinline__ void put_ref(const Fp<P>& a, uint64_t* dst) {
-  uint32_t w[8];
-  to_ref(a, w);
-  store_words(dst, 0, w);
-}
-template <class F>
-__device__ __forceinline__ void put_ref(const Fp2<F>& a, uint64_t* dst) { put_ref(a.c0, dst); put_ref(a.c1, dst + 4); }
-
 // one lane per scalar: MSB-first double-and-add on the generator, then one Fermat inversion to affine
 template <class F, class SP, int E64>
 __global__ void __launch_bounds__(64) k_fixed_base_mul(const uint64_t* __restrict__ k, size_t n, uint64_t* __restrict__ out_xy, uint8_t* __restrict__ out_inf) {
@@ -68,28 +58,10 @@ __global__ void __launch_bounds__(64) k_fixed_base_mul(const uint64_t* __restric
     acc = double_xyzz(acc);
     if ((e[b >> 5] >> (b & 31)) & 1) acc = add_mixed(acc, g);
   }
-  Affine<F> a;
-  uint64_t* dst = out_xy + i * 2 * E64;
-  if (to_affine(acc, a)) {
-    put_ref(a.x, dst);
-    put_ref(a.y, dst + E64);
-    out_inf[i] = 0;
-  } else {                                   // (0, 1, inf): macros/curve/weierstrass/group.rs:22-26
-    put_ref(F::zero(), dst);
-    put_ref(F::one(), dst + E64);
-    out_inf[i] = 1;
-  }
+  put_affine_abi(acc, out_xy + i * 2 * E64, out_inf + i);
 }
 
 // ---- host curve helpers (assembly of the proof, prover.rs:71-98) ---------------------------------------
-template <class HF, int E>
-Affine<HF> h_load_aff(const uint64_t* p);
-template <>
-Affine<HostFq> h_load_aff<HostFq, 4>(const uint64_t* p) { return {HostFq::from_words(p), HostFq::from_words(p + 4)}; }
-template <>
-Affine<HostFq2> h_load_aff<HostFq2, 8>(const uint64_t* p) {
-  return {{HostFq::from_words(p), HostFq::from_words(p + 4)}, {HostFq::from_words(p + 8), HostFq::from_words(p + 12)}};
-}
 // ABI projective (x, y, z in {0, 1}) -> XYZZ
 template <class HF>
 XYZZ<HF> h_from_abi(const Affine<HF>& a, bool inf) { return inf ? XYZZ<HF>::identity() : from_affine(a); }
@@ -116,14 +88,6 @@ XYZZ<HF> h_scalar_mul2(const XYZZ<HF>& p, const uint64_t k1[4], const XYZZ<HF>& 
     else if (b2) acc = add_xyzz(acc, q);
   }
   return acc;
-}
-void h_store(const HostFq& a, uint64_t* w) { a.to_words(w); }
-void h_store(const HostFq2& a, uint64_t* w) { a.c0.to_words(w); a.c1.to_words(w + 4); }
-template <class HF, int E>
-void h_store_affine(const XYZZ<HF>& p, uint64_t* xy, uint8_t* inf) {
-  Affine<HF> a;
-  if (to_affine(p, a)) { h_store(a.x, xy); h_store(a.y, xy + E); *inf = 0; }
-  else { h_store(HF::zero(), xy); h_store(HF::one(), xy + E); *inf = 1; }
 }
 
 // ---- windowed fixed-base multiples (zksnark.rs:57,168-187: 5 m generator multiples per setup) -----------------------
@@ -211,9 +175,9 @@ __global__ void __launch_bounds__(64) k_fb_affine(const uint32_t* __restrict__ t
     const size_t i = first + j;
     const F zzz = RawIO<F>::load(tmp + (size_t)3 * E * n, n, i);
     uint64_t* dst = out_xy + i * 2 * E64;
-    if (is_zero_2p(zzz)) {                            // (0, 1, inf): macros/curve/weierstrass/group.rs:22-26
-      put_ref(F::zero(), dst);
-      put_ref(F::one(), dst + E64);
+    if (is_zero_2p(zzz)) {                            // put_identity_abi's three stores, and below put_affine_abi's, spelled out: through the
+      RefIO<F>::store(F::zero(), dst);                // calls this kernel's unrolled batch loop comes out with other register counts
+      RefIO<F>::store(F::one(), dst + E64);
       out_inf[i] = 1;
       continue;
     }
@@ -221,8 +185,8 @@ __global__ void __launch_bounds__(64) k_fb_affine(const uint32_t* __restrict__ t
     inv_run = mul(inv_run, zzz);
     const F x = RawIO<F>::load(tmp, n, i), y = RawIO<F>::load(tmp + (size_t)E * n, n, i), zz = RawIO<F>::load(tmp + (size_t)2 * E * n, n, i);
     const F zzi = mul(mul(zi, zi), sqr(zz));          // ZZ^-1 = ZZZ^-2 * ZZ^2   (ZZ^3 = ZZZ^2)
-    put_ref(mul(x, zzi), dst);
-    put_ref(mul(y, zi), dst + E64);
+    RefIO<F>::store(mul(x, zzi), dst);
+    RefIO<F>::store(mul(y, zi), dst + E64);
     out_inf[i] = 0;
   }
 }
@@ -257,7 +221,7 @@ int fixed_base_t(kg_ctx* ctx, int curve, const uint64_t* d_k, size_t n, uint64_t
     hipError_t e = hipMemcpyAsync(d_tk, hk.data(), tn * 32, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return set_err(ctx, KG_ERR_HIP, "fixed-base table upload", e);
-    int rc = kg_field_vec_op(ctx, curve == KG_GRUMPKIN ? KG_FQ : KG_FR, KG_OP_TO_MONT, d_tk, nullptr, d_tk, tn);
+    int rc = kg_field_vec_op(ctx, scalar_field(curve), KG_OP_TO_MONT, d_tk, nullptr, d_tk, tn);
     if (rc == KG_OK) {
       hipLaunchKernelGGL((k_fixed_base_mul<F, SP, E64>), dim3((unsigned)((tn + 63) / 64)), dim3(64), 0, st, d_tk, tn, d_txy, d_tinf);
       hipLaunchKernelGGL((k_fb_pack<F, E64>), dim3((unsigned)((tn + 63) / 64)), dim3(64), 0, st, d_txy, tn, table);
@@ -282,13 +246,14 @@ extern "C" {
 
 int kg_fixed_base_mul(kg_ctx* ctx, int curve, const uint64_t* d_k, size_t n, uint64_t* d_out_xy, uint8_t* d_out_inf) {
   return kg::kg_guarded(ctx, [&]() -> int {              // (the table construction holds a std::vector)
-  if (!ctx || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!ctx || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   if (n == 0) return KG_OK;
   if (!d_k || !d_out_xy || !d_out_inf) return KG_ERR_BAD_ARG;
   KG_HIP(ctx, hipSetDevice(ctx->device));
-  if (curve == KG_G1) return fixed_base_t<Fq, FrParams, 4>(ctx, curve, d_k, n, d_out_xy, d_out_inf);
-  if (curve == KG_GRUMPKIN) return fixed_base_t<Fr, FqParams, 4>(ctx, curve, d_k, n, d_out_xy, d_out_inf);
-  return fixed_base_t<Fq2, FrParams, 8>(ctx, curve, d_k, n, d_out_xy, d_out_inf);
+  return with_curve(curve, [&](auto cfg) {
+    using D = CurveDev<decltype(cfg)>;
+    return fixed_base_t<typename D::F, typename D::SP, decltype(cfg)::E64>(ctx, curve, d_k, n, d_out_xy, d_out_inf);
+  });
   });
 }
 
@@ -617,9 +582,9 @@ void start_blinding(WorkerPool* workers, const kg_groth16_crs& vk, const uint64_
   const HostFr rk = mul(rm, raw_one), sk = mul(sm, raw_one), rsk = mul(mul(rm, sm), raw_one);   // out of Montgomery form
   bl->rk = rk; bl->sk = sk;
   bl->started = true;
-  const XYZZ<HostFq> alpha = from_affine(h_load_aff<HostFq, 4>(vk.alpha_g1)), beta1 = from_affine(h_load_aff<HostFq, 4>(vk.beta_g1)),
-                     delta1 = from_affine(h_load_aff<HostFq, 4>(vk.delta_g1));
-  const XYZZ<HostFq2> beta2 = from_affine(h_load_aff<HostFq2, 8>(vk.beta_g2)), delta2 = from_affine(h_load_aff<HostFq2, 8>(vk.delta_g2));
+  const XYZZ<HostFq> alpha = from_affine(host_load_affine<G1Cfg>(vk.alpha_g1)), beta1 = from_affine(host_load_affine<G1Cfg>(vk.beta_g1)),
+                     delta1 = from_affine(host_load_affine<G1Cfg>(vk.delta_g1));
+  const XYZZ<HostFq2> beta2 = from_affine(host_load_affine<G2Cfg>(vk.beta_g2)), delta2 = from_affine(host_load_affine<G2Cfg>(vk.delta_g2));
   auto chain_b = [bl, delta2, beta2, sk]() -> int { bl->g_b = add_xyzz(h_scalar_mul(delta2, sk.v), beta2); return KG_OK; };              // :76
   auto chain_a = [bl, delta1, alpha, rk, rsk]() -> int {                                                                                  // :75, first term of :77
     bl->g_a = add_xyzz(h_scalar_mul(delta1, rk.v), alpha);
@@ -653,12 +618,12 @@ int assemble_proof(WorkerPool* workers, const kg_groth16_crs& vk, const uint64_t
   auto join = [&](std::future<int>& f) { if (f.valid()) { int r2 = f.get(); if (rc == KG_OK) rc = r2; } };
   auto g1pt = [](const uint64_t* xyz) {
     bool pinf = !(xyz[8] | xyz[9] | xyz[10] | xyz[11]);
-    return h_from_abi<HostFq>(h_load_aff<HostFq, 4>(xyz), pinf);
+    return h_from_abi<HostFq>(host_load_affine<G1Cfg>(xyz), pinf);
   };
   auto g2pt = [](const uint64_t* xyz) {
     bool pinf = true;
     for (int i = 16; i < 24; ++i) pinf = pinf && xyz[i] == 0;
-    return h_from_abi<HostFq2>(h_load_aff<HostFq2, 8>(xyz), pinf);
+    return h_from_abi<HostFq2>(host_load_affine<G2Cfg>(xyz), pinf);
   };
   // everything that does not need h's MSM is assembled while the device is still working on it -- s A + r B1 (another 255-step chain) as soon
   // as the two G1 sums are there, under the G2 MSM's host finish (three times a G1 one: the last of the four to arrive)
@@ -672,7 +637,7 @@ int assemble_proof(WorkerPool* workers, const kg_groth16_crs& vk, const uint64_t
   host_trace("proof: chains done");
   if (go) {
     g_a = add_xyzz(bl->g_a, g1pt(ai));                                                                   // :81
-    h_store_affine<HostFq, 4>(g_a, proof, inf);
+    store_affine<G1Cfg>(g_a, proof, inf);
     g_b = bl->g_b;
     g_c = add_xyzz(bl->rs_delta, bl->sa_rb);                                                             // :77
   }
@@ -682,7 +647,7 @@ int assemble_proof(WorkerPool* workers, const kg_groth16_crs& vk, const uint64_t
     g_b = add_xyzz(g_b, g2pt(b2i));                                                                      // :88
     g_c = add_xyzz(g_c, sa_rb1);
     g_c = add_xyzz(g_c, g1pt(l_p));                                                                      // :92 (l part)
-    h_store_affine<HostFq2, 8>(g_b, proof + 8, inf + 1);
+    store_affine<G2Cfg>(g_b, proof + 8, inf + 1);
   }
   host_trace("proof: B stored");
   join(j_h->f_q);
@@ -690,7 +655,7 @@ int assemble_proof(WorkerPool* workers, const kg_groth16_crs& vk, const uint64_t
   if (rc != KG_OK) return rc;
   if (bad_delta) return KG_ERR_CRS;                     // prover.rs:67-69 (the message is set by prove_collect, on the caller's thread)
   g_c = add_xyzz(g_c, g1pt(q_p));                                                                        // :92 (h part)
-  h_store_affine<HostFq, 4>(g_c, proof + 24, inf + 2);
+  store_affine<G1Cfg>(g_c, proof + 24, inf + 2);
   host_trace("proof: assembled");
   return KG_OK;
 }

@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(G16_NT) k_g16_b_g2(G16VkG2 vk, const uint64_t*
 #pragma unroll
   for (int i = 0; i < 4; ++i) load_words(sb2, 4 * proof + i, w + 8 * i);
   const XYZZ<Fq2> b = g16_point_ab(s_delta, g16_g2_point(vk.beta2, false), g16_g2_point(w, sb2_inf[proof] != 0));
-  g16_put_affine<Fq2, 8>(b, proofs + proof * 32 + 8, inf + proof * 3 + 1);
+  put_affine_abi(b, proofs + proof * 32 + 8, inf + proof * 3 + 1);
 }
 
 // The finishing lane of a proof in G1: A = chain 0 + alpha + Sa -> words 0 .. 7, C = chains 1 + 2 + 3 + Sl + Sh -> words 24 .. 31
@@ -133,10 +133,10 @@ __global__ void __launch_bounds__(G16_NT) k_g16_finish_g1(G16VkG1 vk, const uint
     return g16_g1_point(w, f[proof] != 0);
   };
   const XYZZ<Fq> a = g16_point_ab(PointIO<Fq>::load(chains, lanes, t0 + G16_ROLE_R_DELTA), g16_g1_point(vk.alpha, false), sum(sa, sa_inf));
-  g16_put_affine<Fq, 4>(a, proofs + proof * 32, inf + proof * 3);
+  put_affine_abi(a, proofs + proof * 32, inf + proof * 3);
   const XYZZ<Fq> c = g16_point_c(PointIO<Fq>::load(chains, lanes, t0 + G16_ROLE_RS_DELTA), PointIO<Fq>::load(chains, lanes, t0 + G16_ROLE_VK),
                                  PointIO<Fq>::load(chains, lanes, t0 + G16_ROLE_SUMS), sum(sl, sl_inf), sum(sh, sh_inf));
-  g16_put_affine<Fq, 4>(c, proofs + proof * 32 + 24, inf + proof * 3 + 2);
+  put_affine_abi(c, proofs + proof * 32 + 24, inf + proof * 3 + 2);
 }
 
 void vk_words(const uint64_t* src, int n64, uint32_t* dst) {

@@ -5,17 +5,32 @@
 // the host finish).  Replaces groth16/src/msm.rs:6-48.
 #pragma once
 #include "common.h"
-#include "host_fp.h"
+#include "curve_cfg.h"
 #include "fp2s.h"
 #include "msm_internal.h"
 
 namespace kg {
-namespace msm {
-namespace {        // internal linkage: the kernels of a header exist once per translation unit that includes it
 
-struct G1Cfg { using F = Fq; using KF = Fq; using SP = FrParams; using HF = HostFq; static constexpr int E64 = 4; static constexpr int ID = KG_G1; };
-struct GkCfg { using F = Fr; using KF = Fr; using SP = FqParams; using HF = HostFr; static constexpr int E64 = 4; static constexpr int ID = KG_GRUMPKIN; };
-struct G2Cfg { using F = Fq2; using KF = Fp2S<Fq>; using SP = FrParams; using HF = HostFq2; static constexpr int E64 = 8; static constexpr int ID = KG_G2; };
+// The device side of a curve configuration (curve_cfg.h): F the field of the coordinates, KF the field type of the reduction kernels
+// (Fq2: a lane pair per task, fp2s.h), SP the parameters of the scalar field.  with_curve(curve, [&](auto cfg) { using D = CurveDev<decltype(cfg)>; ... })
+template <class Cfg> struct CurveDev;
+template <> struct CurveDev<G1Cfg> { using F = Fq; using KF = Fq; using SP = FrParams; };
+template <> struct CurveDev<GkCfg> { using F = Fr; using KF = Fr; using SP = FqParams; };
+template <> struct CurveDev<G2Cfg> { using F = Fq2; using KF = Fp2S<Fq>; using SP = FrParams; };
+template <class Cfg> constexpr bool curve_dev_ok() {
+  using F = typename CurveDev<Cfg>::F;
+  return RefIO<F>::W64 == coord_words64(Cfg::ID) && PointIO<F>::NW == raw_xyzz_words32(Cfg::ID);
+}
+static_assert(curve_dev_ok<G1Cfg>() && curve_dev_ok<GkCfg>() && curve_dev_ok<G2Cfg>(), "msm_common.h: the device types' word counts are curve_layout.h's");
+
+namespace msm {
+// A whole configuration, host and device side: what the long pipeline's templates (msm_run_multi_t, the reduction probe) take as Cfg
+template <class Cfg> struct DevCfg : Cfg, CurveDev<Cfg> {};
+using G1Cfg = DevCfg<kg::G1Cfg>;
+using GkCfg = DevCfg<kg::GkCfg>;
+using G2Cfg = DevCfg<kg::G2Cfg>;
+
+namespace {        // internal linkage: the kernels of a header exist once per translation unit that includes it
 
 constexpr uint32_t INF_BIT = 0x80000000u;   // bit 255 of the packed x coordinate marks an identity base
 

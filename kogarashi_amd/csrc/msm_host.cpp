@@ -5,7 +5,7 @@
 //
 // Replaces the call shapes of groth16/src/msm.rs:6-48 (msm_curve_addition) and nova/src/pedersen.rs:15-20 (commit).
 #include "common.h"
-#include "host_fp.h"
+#include "host_point.h"
 #include "msm_internal.h"
 #include <algorithm>
 #include <chrono>
@@ -16,47 +16,6 @@
 #include <thread>
 
 using namespace kg;
-
-namespace {
-
-struct G1Cfg { using HF = HostFq; static constexpr int E64 = 4; static constexpr int ID = KG_G1; };
-struct GkCfg { using HF = HostFr; static constexpr int E64 = 4; static constexpr int ID = KG_GRUMPKIN; };
-struct G2Cfg { using HF = HostFq2; static constexpr int E64 = 8; static constexpr int ID = KG_G2; };
-
-template <class HF> struct HostIO;
-template <class P> struct HostIO<HostFp<P>> {
-  static HostFp<P> load(const uint64_t* w) { return HostFp<P>::from_words(w); }
-  static void store(const HostFp<P>& a, uint64_t* w) { a.to_words(w); }
-};
-template <class F> struct HostIO<Fp2<F>> {
-  static Fp2<F> load(const uint64_t* w) { return {HostIO<F>::load(w), HostIO<F>::load(w + 4)}; }
-  static void store(const Fp2<F>& a, uint64_t* w) { HostIO<F>::store(a.c0, w); HostIO<F>::store(a.c1, w + 4); }
-};
-
-template <class Cfg>
-XYZZ<typename Cfg::HF> host_load_point(const uint64_t* p) {
-  using HF = typename Cfg::HF;
-  constexpr int E = Cfg::E64;
-  return {HostIO<HF>::load(p), HostIO<HF>::load(p + E), HostIO<HF>::load(p + 2 * E), HostIO<HF>::load(p + 3 * E)};
-}
-
-template <class Cfg>
-void store_projective(const XYZZ<typename Cfg::HF>& p, uint64_t* out_xyz) {
-  using HF = typename Cfg::HF;
-  constexpr int E = Cfg::E64;
-  Affine<HF> a;
-  if (!to_affine(p, a)) {                        // (0, 1, 0): macros/curve/weierstrass/group.rs:106-110
-    HostIO<HF>::store(HF::zero(), out_xyz);
-    HostIO<HF>::store(HF::one(), out_xyz + E);
-    HostIO<HF>::store(HF::zero(), out_xyz + 2 * E);
-    return;
-  }
-  HostIO<HF>::store(a.x, out_xyz);
-  HostIO<HF>::store(a.y, out_xyz + E);
-  HostIO<HF>::store(HF::one(), out_xyz + 2 * E);
-}
-
-}  // namespace
 
 namespace kg {
 
@@ -105,18 +64,11 @@ int msm_finish_t(kg_ctx* ctx, const int* slots, int nslots, uint64_t* out_xyz) {
 
 int msm_finish_groups(kg_ctx* ctx, int curve, const int* slots, int nslots, uint64_t* out_xyz) {
   if (nslots < 1) return KG_ERR_BAD_ARG;
-  switch (curve) {
-    case KG_G1: return msm_finish_t<G1Cfg>(ctx, slots, nslots, out_xyz);
-    case KG_GRUMPKIN: return msm_finish_t<GkCfg>(ctx, slots, nslots, out_xyz);
-    case KG_G2: return msm_finish_t<G2Cfg>(ctx, slots, nslots, out_xyz);
-    default: return KG_ERR_BAD_ARG;
-  }
+  return with_curve(curve, [&](auto cfg) { return msm_finish_t<decltype(cfg)>(ctx, slots, nslots, out_xyz); });
 }
 int msm_finish(kg_ctx* ctx, int curve, int slot, uint64_t* out_xyz) { return msm_finish_groups(ctx, curve, &slot, 1, out_xyz); }
 void msm_identity(int curve, uint64_t* out_xyz) {
-  if (curve == KG_G2) store_projective<G2Cfg>(XYZZ<HostFq2>::identity(), out_xyz);
-  else if (curve == KG_GRUMPKIN) store_projective<GkCfg>(XYZZ<HostFr>::identity(), out_xyz);
-  else store_projective<G1Cfg>(XYZZ<HostFq>::identity(), out_xyz);
+  with_curve(curve, [&](auto cfg) { store_projective<decltype(cfg)>(XYZZ<typename decltype(cfg)::HF>::identity(), out_xyz); });
 }
 
 }  // namespace kg
@@ -126,17 +78,12 @@ namespace {
 template <class Cfg>
 int sum_affine_impl(const uint64_t* pts, const uint8_t* inf, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
   using HF = typename Cfg::HF;
-  constexpr int E = Cfg::E64;
   XYZZ<HF> acc = XYZZ<HF>::identity();
   for (size_t i = 0; i < count; ++i) {
     if (inf && inf[i]) continue;
-    Affine<HF> a{HostIO<HF>::load(pts + i * 2 * E), HostIO<HF>::load(pts + i * 2 * E + E)};
-    acc = add_mixed(acc, a);
+    acc = add_mixed(acc, host_load_affine<Cfg>(pts + i * 2 * Cfg::E64));
   }
-  uint64_t xyz[3 * 8];
-  store_projective<Cfg>(acc, xyz);
-  std::memcpy(out_xy, xyz, 2 * E * 8);
-  *out_inf = is_identity(acc) ? 1 : 0;
+  store_affine<Cfg>(acc, out_xy, out_inf);
   return KG_OK;
 }
 
@@ -146,7 +93,7 @@ extern "C" {
 
 // Sum of the slices' results (projective (x, y, 1) / (0, 1, 0) each) -> the same form
 static int sum_slices(kg_ctx* ctx, int curve, const uint64_t (*part)[24], int K, uint64_t* out_xyz) {
-  const int E = curve == KG_G2 ? 8 : 4;
+  const int E = (int)coord_words64(curve);
   if (K == 1) { std::memcpy(out_xyz, part[0], (size_t)3 * E * 8); return KG_OK; }
   uint64_t pts[kg_ctx::UP_SLICES * 16];
   uint8_t pinf[kg_ctx::UP_SLICES];
@@ -173,7 +120,7 @@ static int sum_slices(kg_ctx* ctx, int curve, const uint64_t (*part)[24], int K,
 // window width of the whole (c = 17), so the number of additions does not change; the extra bucket reductions are hidden.
 static int msm_sliced(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n, uint64_t* out_xyz) {
   constexpr int K = 4;
-  const size_t pw = curve == KG_G2 ? 16 : 8;               // u64 words per base
+  const size_t pw = affine_words64(curve);                 // u64 words per base
   size_t lo[K + 1];
   for (int j = 0; j <= K; ++j) lo[j] = n / K * j + (j == K ? n % K : 0);
   const int saved_window = ctx->msm_window;
@@ -183,7 +130,7 @@ static int msm_sliced(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uin
   std::future<int> fin[K];
   kg::WaitAll fin_done{fin, K};                            // the finishes write into part[]
   int rc = KG_OK;
-  const int sfield = curve == KG_GRUMPKIN ? KG_FQ : KG_FR;
+  const int sfield = scalar_field(curve);
   for (int j = 0; j < K && rc == KG_OK; ++j) {
     const size_t a = lo[j], cnt = lo[j + 1] - lo[j];
     kg::MsmSorted S;
@@ -220,7 +167,7 @@ static int msm_grouped(kg_ctx* ctx, int curve, const uint64_t* d_bases, const ui
   // apart, share the chip from the start and neither finishes early: 1.93-2.04 ms against 1.77-1.85 with both sorts in turn on the
   // scalar queue (2^20, same box, alternating runs; unsplit 1.85-1.90)
   const int main_first = ctx->tune.group_main_first;
-  KG_TRY(kg::msm_sort_begin(ctx, curve == KG_GRUMPKIN ? KG_FQ : KG_FR, d_scalars, n, &Q, false, 0, 1, NG, gw, main_first != 0));
+  KG_TRY(kg::msm_sort_begin(ctx, scalar_field(curve), d_scalars, n, &Q, false, 0, 1, NG, gw, main_first != 0));
   if (main_first == 1) {                                   // the scalar queue (the later groups' sorts) follows the conversion
     KG_HIP(ctx, hipEventRecord(ctx->ev_prep, ctx->stream));
     KG_HIP(ctx, hipStreamWaitEvent(ctx->sort_stream, ctx->ev_prep, 0));
@@ -234,7 +181,7 @@ static int msm_grouped(kg_ctx* ctx, int curve, const uint64_t* d_bases, const ui
   const bool f64 = resident_fmt64(n);
   if (!resident && kg::acc_abi_bases(ctx, curve, d_bases, d_inf, n)) resident = true;      // gathered as the caller holds them: msm_run_multi_t applies the same rule to the job
   if (!resident) {
-    const size_t bytes = n * (f64 ? (curve == KG_G2 ? 128 : 64) : (curve == KG_G2 ? 144 : 72));
+    const size_t bytes = n * resident_words32(curve, f64) * 4;
     KG_TRY(ctx->ws_pb.ensure(DevMem{ctx, "resident-bases allocation"}, bytes, bytes / 8));
     hipStream_t cq = ctx->side_stream;
     if (!ctx->inputs_complete) {                          // stream semantics: the bases may still be in flight on the main queue
@@ -285,7 +232,7 @@ static int msm_blocking(kg_ctx* ctx, int curve, const uint64_t* d_bases, const u
 
 int kg_msm(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n, uint64_t* out_xyz) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || !out_xyz || (n && (!d_bases || !d_scalars)) || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!ctx || !out_xyz || (n && (!d_bases || !d_scalars)) || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   if (n == 0) { kg::msm_identity(curve, out_xyz); return KG_OK; }
   return msm_blocking(ctx, curve, d_bases, d_inf, d_scalars, n, out_xyz);
   });
@@ -313,7 +260,7 @@ static int msm_blocking(kg_ctx* ctx, int curve, const uint64_t* d_bases, const u
     if (NG > 1) return msm_grouped(ctx, curve, d_bases, d_inf, d_scalars, n, gw, NG, out_xyz);
   }
   ctx->sort_alone = true;                                 // a blocking call: its sort is all the device has to do
-  const int rs = kg::msm_sort(ctx, curve == KG_GRUMPKIN ? KG_FQ : KG_FR, d_scalars, n, &S, false, mc);
+  const int rs = kg::msm_sort(ctx, scalar_field(curve), d_scalars, n, &S, false, mc);
   ctx->sort_alone = false;
   KG_TRY(rs);
   S.tail_alone = true;                                    // a blocking call: nothing runs beside its reduction
@@ -327,13 +274,13 @@ int kg_msm_table_window(size_t msm_len) { return kg::merged_window(nullptr, msm_
 
 int kg_bases_register(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t n) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!ctx || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   if (n == 0) return KG_OK;                         // nothing to convert (e.g. an empty CRS vector)
   if (!d_bases) return KG_ERR_BAD_ARG;
   KG_HIP(ctx, hipSetDevice(ctx->device));
   kg_bases_unregister(ctx, d_bases);
   const bool fmt64 = resident_fmt64(n);
-  const size_t pw = fmt64 ? (curve == KG_G2 ? 32 : 16) : (curve == KG_G2 ? 36 : 18);
+  const size_t pw = resident_words32(curve, fmt64);
   kg_ctx::Registered reg{d_bases, d_inf, n, curve};
   reg.fmt64 = fmt64;
   KG_TRY(reg.packed.ensure(DevMem{ctx, "registered-bases allocation"}, n * pw * 4));
@@ -373,7 +320,7 @@ int kg_bases_precompute(kg_ctx* ctx, const uint64_t* d_bases, size_t msm_len) {
   r->table_c = r->table_W = 0;
   const int W = (255 + c - 1) / c;
   const bool t64 = table_fmt64();
-  const size_t pw = t64 ? (r->curve == KG_G2 ? 32 : 16) : (r->curve == KG_G2 ? 36 : 18), row = r->n * pw;
+  const size_t pw = resident_words32(r->curve, t64), row = r->n * pw;
   KG_TRY(r->table.ensure(DevMem{ctx, "window table allocation"}, (size_t)W * row * 4));
   uint32_t* const table = r->table.as<uint32_t>();
   hipStream_t st = ctx->stream;
@@ -392,7 +339,7 @@ int kg_bases_precompute(kg_ctx* ctx, const uint64_t* d_bases, size_t msm_len) {
 
 int kg_msm_begin(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n, int ticket) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || (n && (!d_bases || !d_scalars)) || curve < 0 || curve > KG_G2 || ticket < 0 || ticket > 3) return KG_ERR_BAD_ARG;
+  if (!ctx || (n && (!d_bases || !d_scalars)) || !curve_ok(curve) || ticket < 0 || ticket > 3) return KG_ERR_BAD_ARG;
   ctx->ticket_n[ticket] = n;
   if (n == 0) return KG_OK;
   int sc = 0, sr = 0;
@@ -413,7 +360,7 @@ int kg_msm_begin(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t*
   }
   kg::MsmSorted S;
   const int mc = kg::has_window_table(ctx, curve, d_bases, d_inf, n, n) ? kg::merged_window(ctx, n) : 0;
-  KG_TRY(kg::msm_sort(ctx, curve == KG_GRUMPKIN ? KG_FQ : KG_FR, d_scalars, n, &S, false, mc));
+  KG_TRY(kg::msm_sort(ctx, scalar_field(curve), d_scalars, n, &S, false, mc));
   // KG_PIPE_ACCQ=2 (experiment, round 4): MSMs in flight alternate between two accumulation queues on the same compute pipe, so that the
   // next launch's first waves fill the tail in which this one drains.  Measured level to slightly worse (1.347 -> 1.358 ms per step,
   // three alternating runs): a two-round launch with longest-first tasks has little tail to fill.  Off.
@@ -429,12 +376,12 @@ int kg_msm_begin(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t*
 
 int kg_msm_end(kg_ctx* ctx, int curve, int ticket, uint64_t* out_xyz) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || !out_xyz || curve < 0 || curve > KG_G2 || ticket < 0 || ticket > 3) return KG_ERR_BAD_ARG;
+  if (!ctx || !out_xyz || !curve_ok(curve) || ticket < 0 || ticket > 3) return KG_ERR_BAD_ARG;
   if (ctx->ticket_n[ticket] == 0) { kg::msm_identity(curve, out_xyz); return KG_OK; }
   if (!ctx->ticket_fut[ticket].valid()) return kg::set_err(ctx, KG_ERR_BAD_ARG, "kg_msm_end without a matching kg_msm_begin");
   const int rc = ctx->ticket_fut[ticket].get();
   if (rc != KG_OK) return rc;
-  std::memcpy(out_xyz, ctx->ticket_out[ticket], (curve == KG_G2 ? 24 : 12) * 8);
+  std::memcpy(out_xyz, ctx->ticket_out[ticket], projective_words64(curve) * 8);
   return KG_OK;
   });
 }
@@ -489,7 +436,7 @@ static int msm_host_impl(kg_ctx* ctx, int curve, const uint64_t* bases, const ui
                          uint64_t* out_xyz) {
   KG_HIP(ctx, hipSetDevice(ctx->device));
   host_trace("host: enter");
-  const size_t pb = curve == KG_G2 ? 128 : 64;             // bytes per base
+  const size_t pb = affine_words64(curve) * 8;             // bytes per base
   const DevMem up_mem{ctx, "upload buffer allocation"};
   if (!bases_on_device) {
     KG_TRY(ctx->up_buf[0].ensure(up_mem, n * pb, n * pb / 8));
@@ -573,7 +520,7 @@ static int msm_host_impl(kg_ctx* ctx, int curve, const uint64_t* bases, const ui
   std::future<int> fin[kg_ctx::UP_SLICES];
   kg::WaitAll fin_done{fin, kg_ctx::UP_SLICES};            // the finishes write into part[]
   int rc = KG_OK;
-  const int sfield = curve == KG_GRUMPKIN ? KG_FQ : KG_FR;
+  const int sfield = scalar_field(curve);
   const bool was_alone = ctx->sort_alone;
   for (int j = 0; j < K && rc == KG_OK; ++j) {
     const size_t a = lo[j], cnt = lo[j + 1] - lo[j];
@@ -623,7 +570,7 @@ int kg_msm_host_slices(size_t n, int scalars_only, size_t* lo) {
 
 int kg_msm_host(kg_ctx* ctx, int curve, const uint64_t* h_bases, const uint8_t* h_inf, const uint64_t* h_scalars, size_t n, uint64_t* out_xyz) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || !out_xyz || (n && (!h_bases || !h_scalars)) || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!ctx || !out_xyz || (n && (!h_bases || !h_scalars)) || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   if (n == 0) return kg_msm(ctx, curve, nullptr, nullptr, nullptr, 0, out_xyz);
   return msm_host_impl(ctx, curve, h_bases, h_inf, false, h_scalars, n, out_xyz);
   });
@@ -631,14 +578,14 @@ int kg_msm_host(kg_ctx* ctx, int curve, const uint64_t* h_bases, const uint8_t* 
 
 int kg_msm_host_scalars(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* h_scalars, size_t n, uint64_t* out_xyz) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || !out_xyz || (n && (!d_bases || !h_scalars)) || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!ctx || !out_xyz || (n && (!d_bases || !h_scalars)) || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   if (n == 0) return kg_msm(ctx, curve, nullptr, nullptr, nullptr, 0, out_xyz);
   return msm_host_impl(ctx, curve, d_bases, d_inf, true, h_scalars, n, out_xyz);
   });
 }
 
 static void xyz_to_commit(int curve, const uint64_t* xyz, uint64_t* out_xy, uint8_t* out_inf) {
-  const int E = curve == KG_G2 ? 8 : 4;
+  const int E = (int)coord_words64(curve);
   std::memcpy(out_xy, xyz, 2 * E * 8);
   bool z0 = true;
   for (int i = 0; i < E; ++i) z0 = z0 && xyz[2 * E + i] == 0;
@@ -648,7 +595,7 @@ static void xyz_to_commit(int curve, const uint64_t* xyz, uint64_t* out_xy, uint
 int kg_commit_host_scalars(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* h_scalars, size_t n,
                            uint64_t* out_xy, uint8_t* out_inf) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || !out_xy || !out_inf || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!ctx || !out_xy || !out_inf || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   uint64_t xyz[24];
   KG_TRY(kg_msm_host_scalars(ctx, curve, d_bases, d_inf, h_scalars, n, xyz));
   xyz_to_commit(curve, xyz, out_xy, out_inf);
@@ -659,7 +606,7 @@ int kg_commit_host_scalars(kg_ctx* ctx, int curve, const uint64_t* d_bases, cons
 int kg_commit(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n,
               uint64_t* out_xy, uint8_t* out_inf) {
   return kg::kg_guarded(ctx, [&]() -> int {
-  if (!ctx || !out_xy || !out_inf || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!ctx || !out_xy || !out_inf || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   uint64_t xyz[24];
   KG_TRY(kg_msm(ctx, curve, d_bases, d_inf, d_scalars, n, xyz));
   xyz_to_commit(curve, xyz, out_xy, out_inf);
@@ -670,12 +617,7 @@ int kg_commit(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_
 int kg_points_sum_affine(kg_ctx* ctx, int curve, const uint64_t* pts, const uint8_t* inf, size_t count, uint64_t* out_xy, uint8_t* out_inf) {
   (void)ctx;
   if (!out_xy || !out_inf || (count && !pts)) return KG_ERR_BAD_ARG;
-  switch (curve) {
-    case KG_G1: return sum_affine_impl<G1Cfg>(pts, inf, count, out_xy, out_inf);
-    case KG_GRUMPKIN: return sum_affine_impl<GkCfg>(pts, inf, count, out_xy, out_inf);
-    case KG_G2: return sum_affine_impl<G2Cfg>(pts, inf, count, out_xy, out_inf);
-    default: return KG_ERR_BAD_ARG;
-  }
+  return with_curve(curve, [&](auto cfg) { return sum_affine_impl<decltype(cfg)>(pts, inf, count, out_xy, out_inf); });
 }
 
 }  // extern "C"

@@ -10,18 +10,16 @@ using namespace kg::msm;
 
 namespace kg {
 void prep_bases_enqueue(int curve, hipStream_t st, const uint64_t* d_bases, const uint8_t* d_inf, size_t n, uint32_t* out, bool fmt64) {
-  if (curve == KG_G1) launch_prep_bases<Fq>(st, d_bases, d_inf, n, out, fmt64);
-  else if (curve == KG_GRUMPKIN) launch_prep_bases<Fr>(st, d_bases, d_inf, n, out, fmt64);
-  else launch_prep_bases<Fq2>(st, d_bases, d_inf, n, out, fmt64);
+  with_curve(curve, [&](auto cfg) { launch_prep_bases<typename CurveDev<decltype(cfg)>::F>(st, d_bases, d_inf, n, out, fmt64); });
 }
 bool acc_abi_bases(const kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t n) {
   return ctx->tune.acc_abi_bases != 0 && (curve == KG_G1 || curve == KG_GRUMPKIN) && !d_inf && resident_fmt64(n) && ((uintptr_t)d_bases & 15) == 0;
 }
 void table_next_enqueue(int curve, hipStream_t st, const uint32_t* prev, size_t n, int c, uint32_t* next, bool fmt64) {
   const dim3 grid((unsigned)((n + 63) / 64));
-  if (curve == KG_G1) hipLaunchKernelGGL(k_table_next<Fq>, grid, dim3(64), 0, st, prev, n, c, next, fmt64 ? 1 : 0);
-  else if (curve == KG_GRUMPKIN) hipLaunchKernelGGL(k_table_next<Fr>, grid, dim3(64), 0, st, prev, n, c, next, fmt64 ? 1 : 0);
-  else hipLaunchKernelGGL(k_table_next<Fq2>, grid, dim3(64), 0, st, prev, n, c, next, fmt64 ? 1 : 0);
+  with_curve(curve, [&](auto cfg) {
+    hipLaunchKernelGGL(k_table_next<typename CurveDev<decltype(cfg)>::F>, grid, dim3(64), 0, st, prev, n, c, next, fmt64 ? 1 : 0);
+  });
 }
 }  // namespace kg
 
@@ -247,9 +245,7 @@ int msm_run_multi_t(kg_ctx* ctx, const MsmSorted& S, const MsmRunJob* jobs, int 
       // the sums go straight into the slot's pinned host buffer (its device view): no copy kernel behind the tail
       if (S.tail_alone && ctx->tune.coop_tail && len >= 2) {        // nothing beside it: a quad of lanes per addition (k_reduce_tail_coop)
         const size_t lds = tail_coop_lds_bytes<F>(len);
-        static std::atomic<uint64_t> attr_devs{0};      // once per device
-        const uint64_t bit = (uint64_t)1 << (ctx->device & 63);
-        if (!(attr_devs.load() & bit)) { KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_reduce_tail_coop<F, Cfg::E64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_devs |= bit; }
+        KG_TRY((lds_attr_once<k_reduce_tail_coop<F, Cfg::E64>>(ctx, 160 * 1024)));
         hipLaunchKernelGGL((k_reduce_tail_coop<F, Cfg::E64>), dim3((unsigned)(W * narr)), dim3(TailCoopNT<F>::NT), lds, side, pbuf[cur], in_stride, narr, len, c, (uint64_t*)sl.host.mem().dev);
       } else
       if (len == TL) {
@@ -303,12 +299,7 @@ int scalar_queue(kg_ctx* ctx, hipStream_t* out) {
 
 int msm_run_multi(kg_ctx* ctx, const MsmSorted& S, int curve, const MsmRunJob* jobs, int njobs) {
   if (njobs < 1 || njobs > MAX_FUSED) return KG_ERR_BAD_ARG;
-  switch (curve) {
-    case KG_G1: return msm_run_multi_t<G1Cfg>(ctx, S, jobs, njobs);
-    case KG_GRUMPKIN: return msm_run_multi_t<GkCfg>(ctx, S, jobs, njobs);
-    case KG_G2: return msm_run_multi_t<G2Cfg>(ctx, S, jobs, njobs);
-    default: return KG_ERR_BAD_ARG;
-  }
+  return with_curve(curve, [&](auto cfg) { return msm_run_multi_t<DevCfg<decltype(cfg)>>(ctx, S, jobs, njobs); });
 }
 int msm_run(kg_ctx* ctx, const MsmSorted& S, int curve, const uint64_t* d_bases, const uint8_t* d_inf, size_t nbases, uint32_t idx_off, int slot) {
   const MsmRunJob j{d_bases, d_inf, nbases, idx_off, slot, false, nullptr, false};

@@ -2,7 +2,6 @@
 // two launches that leave the W window sums in the result slot's pinned buffer.  Replaces, for n <= 2^12 pairs, the launch chain of
 // msm_sort.hip + msm_run.hip behind kg_msm / kg_msm_begin / kg_commit / the prover (groth16/src/msm.rs:6-48 at the lengths of its own tests).
 #include "msm_small_kernels.h"
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 
@@ -83,14 +82,7 @@ bool msm_small_kt(const kg_ctx* ctx, size_t n) {
 
 template <class F, class SP>
 static int small_launch(kg_ctx* ctx, hipStream_t st, const SmallArgs& a, size_t lds, size_t lds2) {
-  static std::atomic<uint64_t> attr_devs{0};          // once per DEVICE and instance (the attribute belongs to the function on a device): the whole 160 KiB of LDS
-  const uint64_t bit = (uint64_t)1 << (ctx->device & 63);
-  if (!(attr_devs.load() & bit)) {
-    KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_msm_small<F, SP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_msm_small<F, SP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_msm_small_combine<F>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_devs |= bit;
-  }
+  KG_TRY((lds_attr_once<k_msm_small<F, SP, false>, k_msm_small<F, SP, true>, k_msm_small_combine<F>>(ctx, 160 * 1024)));      // the whole 160 KiB of LDS
   if (a.kt) {
     hipLaunchKernelGGL((k_small_prep<SP>), dim3((a.nr + 255) / 256), dim3(256), 0, st, a.scalars, a.nr, a.H, const_cast<uint32_t*>(a.kt), a.spill_cursor, a.W, a.glv, a.inf,
                        const_cast<uint8_t*>(a.meta));
@@ -109,25 +101,16 @@ int msm_small_enqueue(kg_ctx* ctx, hipStream_t st, int curve, const uint64_t* d_
   if (slot < 0 || slot >= kg_ctx::NSLOTS) return set_err(ctx, KG_ERR_BAD_ARG, "bad result slot");
   KG_HIP(ctx, hipSetDevice(ctx->device));
   const bool glv = msm_small_glv(ctx, curve, n);
-  const int W = ((glv ? 128 : 255) + c - 1) / c, NB = 1 << (c - 1 - r), E64 = curve == KG_G2 ? 8 : 4;     // glv: |k1|, |k2| < 2^127
-  const size_t nv = glv ? 2 * n : n;
-  const int NW = curve == KG_G2 ? PointIO<Fq2>::NW : PointIO<Fq>::NW;
-  KG_TRY(ensure_slot(ctx, slot, (size_t)W * 4 * E64 * 8));
+  const int W = ((glv ? 128 : 255) + c - 1) / c, NB = 1 << (c - 1 - r);     // glv: |k1|, |k2| < 2^127
+  const size_t nv = glv ? 2 * n : n, NW = raw_xyzz_words32(curve);
+  KG_TRY(ensure_slot(ctx, slot, (size_t)W * xyzz_words64(curve) * 8));
   kg_ctx::Slot& sl = ctx->slots[slot];
-  SmallArgs a;
-  a.bases = d_bases; a.inf = d_inf; a.scalars = d_scalars; a.n = (uint32_t)nv; a.nr = (uint32_t)n; a.glv = glv ? 1 : 0; a.npl = glv ? 4 : 8; a.meta = nullptr;
-  a.c = c; a.W = W; a.r = r; a.NB = NB;
-  uint32_t H[8];
-  small_bias(c, W, H);
-  for (int j = 0; j < 8; ++j) a.H.w[j] = H[j];
+  SmallArgs a = small_args(d_bases, d_inf, d_scalars, n, glv, c, r, W, NB);
   a.out = (uint64_t*)sl.host.mem().dev;
-  a.planes = nullptr;
-  a.kt = nullptr; a.spill = nullptr; a.spill_cursor = nullptr;
   const bool kt = msm_small_kt(ctx, n);
 #ifdef KG_EXPERIMENTS
   static uint64_t* stamps = nullptr;                  // KG_SMALL_STAMPS=1: the previous call's phase boundaries (workgroup (0, 0)) on stderr
   const bool want_stamps = ctx->tune.small_stamps != 0;
-  a.stamps = nullptr;
   if (want_stamps) {
     if (!stamps) { if (hipHostMalloc((void**)&stamps, 64 * 8, hipHostMallocDefault) != hipSuccess) stamps = nullptr; else memset(stamps, 0, 64 * 8); }
     if (stamps && stamps[7]) {
@@ -139,7 +122,6 @@ int msm_small_enqueue(kg_ctx* ctx, hipStream_t st, int curve, const uint64_t* d_
     a.stamps = stamps;
   }
 #endif
-  size_t lds2 = 0;
   if (NB > 1 || kt) {
     // scratch of the slot: plane points of split windows | the scalars' word planes | spill cursors | spill space of the lists
     const size_t b_planes = ((size_t)W * NB * (SM_MAX_R + 1) * NW * 4 + 255) & ~(size_t)255;
@@ -151,13 +133,13 @@ int msm_small_enqueue(kg_ctx* ctx, hipStream_t st, int curve, const uint64_t* d_
     a.planes = (uint32_t*)ws;
     if (kt) { a.kt = (const uint32_t*)(ws + b_planes); a.spill_cursor = (uint32_t*)(ws + b_planes + b_kt); a.spill = (uint16_t*)(ws + b_planes + b_kt + b_cur); }
     if (kt && glv) a.meta = (const uint8_t*)(ws + b_planes + b_kt + b_cur + b_spill);
-    if (NB > 1) lds2 = curve == KG_G2 ? small_combine_lds_bytes<Fq2>(c, NB) : small_combine_lds_bytes<Fq>(c, NB);
   }
   PhaseScope ph(ctx, "small_msm", st);
-  int rc;
-  if (curve == KG_G1) rc = small_launch<Fq, FrParams>(ctx, st, a, small_lds_bytes<Fq>(a.n, r, kt), lds2);
-  else if (curve == KG_GRUMPKIN) rc = small_launch<Fr, FqParams>(ctx, st, a, small_lds_bytes<Fr>(a.n, r, kt), lds2);
-  else rc = small_launch<Fq2, FrParams>(ctx, st, a, small_lds_bytes<Fq2>(a.n, r, kt), lds2);
+  const int rc = with_curve(curve, [&](auto cfg) {
+    using D = CurveDev<decltype(cfg)>;
+    using F = typename D::F;
+    return small_launch<F, typename D::SP>(ctx, st, a, small_lds_bytes<F>(a.n, r, kt), NB > 1 ? small_combine_lds_bytes<F>(c, NB) : 0);
+  });
   ph.end();
   KG_TRY(rc);
   KG_HIP(ctx, hipEventRecord(sl.done, st));

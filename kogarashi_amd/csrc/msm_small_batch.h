@@ -13,6 +13,7 @@
 #include <climits>
 #include <cstddef>
 #include <cstdint>
+#include "curve_layout.h"
 
 namespace kg {
 
@@ -21,21 +22,16 @@ constexpr size_t MSM_BATCH_GRID_MAX = 65535;                    // a HIP grid's 
 constexpr size_t MSM_BATCH_SCRATCH_CAP = (size_t)64 << 20;      // scratch of one group: at most 64 MiB -- a memory policy: a quarter of what
                                                                 // the batched transform allows itself (ntt_batch.h), the inputs here are short
 constexpr int MSM_BATCH_PLANES = 8;                             // plane points a workgroup of a split window leaves (= SM_MAX_R + 1, asserted in msm_small_batch.hip)
-constexpr int MSM_BATCH_CURVES = 3;                             // KG_G1, KG_GRUMPKIN, KG_G2 = 0, 1, 2
-
-inline bool msm_batch_curve_ok(int curve) { return curve >= 0 && curve < MSM_BATCH_CURVES; }
-inline size_t msm_batch_e64(int curve) { return curve == 2 ? 8 : 4; }                  // u64 words of a coordinate
-inline size_t msm_batch_plane_words(int curve) { return curve == 2 ? 72 : 36; }        // u32 words of a raw XYZZ point (= PointIO<F>::NW)
 
 // The shape the short kernel runs an n-pair vector in (msm_small_plan / msm_small_glv): window width c, 2^r buckets per workgroup,
 // halved scalars or not.  n == 0 is the shape without windows: the finish kernel alone writes the identities.
 struct MsmBatchShape { int curve, c, r; bool glv; size_t n; };
 inline int msm_batch_windows(const MsmBatchShape& s) { return s.n == 0 ? 0 : ((s.glv ? 128 : 255) + s.c - 1) / s.c; }
 inline int msm_batch_ranges(const MsmBatchShape& s) { return s.n == 0 ? 1 : 1 << (s.c - 1 - s.r); }          // NB: workgroups per window
-inline size_t msm_batch_sums_bytes(const MsmBatchShape& s) { return (size_t)msm_batch_windows(s) * 4 * msm_batch_e64(s.curve) * 8; }
+inline size_t msm_batch_sums_bytes(const MsmBatchShape& s) { return (size_t)msm_batch_windows(s) * xyzz_words64(s.curve) * 8; }
 inline size_t msm_batch_planes_bytes(const MsmBatchShape& s) {
   const int NB = msm_batch_ranges(s);
-  return NB > 1 ? (size_t)msm_batch_windows(s) * NB * MSM_BATCH_PLANES * msm_batch_plane_words(s.curve) * 4 : 0;
+  return NB > 1 ? (size_t)msm_batch_windows(s) * NB * MSM_BATCH_PLANES * raw_xyzz_words32(s.curve) * 4 : 0;
 }
 inline size_t msm_batch_vector_bytes(const MsmBatchShape& s) { return msm_batch_sums_bytes(s) + msm_batch_planes_bytes(s); }
 
@@ -65,13 +61,13 @@ inline size_t msm_batch_scratch_bytes(size_t vector_bytes, size_t count) {
 // whenever a pair is read.  Every element count and byte size the call forms must fit a size_t.
 inline bool msm_batch_args_ok(const void* ctx, int curve, const void* d_bases, const void* d_scalars, size_t n, size_t count, size_t stride, const void* d_out_xy,
                               const void* d_out_inf) {
-  if (!ctx || !msm_batch_curve_ok(curve) || stride < n) return false;
+  if (!ctx || !curve_ok(curve) || stride < n) return false;
   if (count == 0) return true;
   if (!d_out_xy || !d_out_inf) return false;
   if (n != 0 && (!d_bases || !d_scalars)) return false;
   if (stride > SIZE_MAX / 32 / count) return false;                               // count * stride scalars of 32 bytes
-  if (count > SIZE_MAX / (16 * msm_batch_e64(curve))) return false;               // count points of 2 coordinates
-  if (n > SIZE_MAX / (16 * msm_batch_e64(curve))) return false;                   // n bases
+  if (count > SIZE_MAX / (8 * affine_words64(curve))) return false;               // count points of 2 coordinates
+  if (n > SIZE_MAX / (8 * affine_words64(curve))) return false;                   // n bases
   return true;
 }
 

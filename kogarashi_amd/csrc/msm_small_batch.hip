@@ -14,7 +14,6 @@
 #include "msm_small_kernels.h"
 #include "msm_small_batch.h"
 #include "msm_small_finish.h"
-#include <atomic>
 #include <climits>
 #include <vector>
 
@@ -22,7 +21,6 @@ using namespace kg;
 using namespace kg::msm;
 
 static_assert(MSM_BATCH_PLANES == SM_MAX_R + 1, "msm_small_batch.h: plane points per workgroup are msm_small_kernels.h's");
-static_assert(PointIO<Fq>::NW == 36 && PointIO<Fq2>::NW == 72 && SmIO<Fq>::E64 == 4 && SmIO<Fq2>::E64 == 8, "msm_small_batch.h: point sizes");
 
 namespace {
 
@@ -47,15 +45,6 @@ struct SmVector {
 template <class F, class SP> constexpr auto k_msm_small_batch = k_msm_small<F, SP, false, SmVector<2>>;
 template <class F> constexpr auto k_msm_small_combine_batch = k_msm_small_combine<F, SmVector<1>>;
 
-template <class P>
-__device__ __forceinline__ void fin_put(const Fp<P>& a, uint64_t* dst) {
-  uint32_t w[8];
-  to_ref(a, w);
-  store_words(dst, 0, w);
-}
-template <class G>
-__device__ __forceinline__ void fin_put(const Fp2<G>& a, uint64_t* dst) { fin_put(a.c0, dst); fin_put(a.c1, dst + 4); }
-
 // One lane per vector: the W window sums of vector i (ABI words, 4 coordinates each) -> its affine point and flag.  W == 0 (empty
 // vectors): every point is the identity.
 constexpr int FIN_NT = 64;
@@ -72,28 +61,8 @@ __global__ void __launch_bounds__(FIN_NT) k_small_finish_batch(const uint64_t* _
     return XYZZ<F>{RefIO<F>::load(s), RefIO<F>::load(s + E), RefIO<F>::load(s + 2 * E), RefIO<F>::load(s + 3 * E)};
   }, p);
   uint64_t* dst = out_xy + i * 2 * E;
-  if (finite) {
-    fin_put(p.x, dst);
-    fin_put(p.y, dst + E);
-    out_inf[i] = 0;
-  } else {                                    // (0, 1) + flag, as kg_fixed_base_mul writes the identity
-    fin_put(F::zero(), dst);
-    fin_put(F::one(), dst + E);
-    out_inf[i] = 1;
-  }
-}
-
-// the whole 160 KiB of LDS for the two shells: once per device and instantiation, like small_launch (msm_small.hip)
-template <class F, class SP>
-int batch_attrs(kg_ctx* ctx) {
-  static std::atomic<uint64_t> attr_devs{0};
-  const uint64_t bit = (uint64_t)1 << (ctx->device & 63);
-  if (!(attr_devs.load() & bit)) {
-    KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_msm_small_batch<F, SP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    KG_HIP(ctx, hipFuncSetAttribute((const void*)(k_msm_small_combine_batch<F>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_devs |= bit;
-  }
-  return KG_OK;
+  if (finite) put_affine_abi(p, dst, out_inf + i);
+  else put_identity_abi<F>(dst, out_inf + i);
 }
 
 // one launch group: `group` vectors whose scalars begin at a.scalars; window sums and planes in the batch scratch `ws`
@@ -102,7 +71,7 @@ int batch_group(kg_ctx* ctx, hipStream_t st, SmallArgs a, const MsmBatchShape& s
   const int W = msm_batch_windows(sh), NB = msm_batch_ranges(sh);
   uint64_t* sums = (uint64_t*)ws;
   if (W > 0) {
-    KG_TRY((batch_attrs<F, SP>(ctx)));
+    KG_TRY((lds_attr_once<k_msm_small_batch<F, SP>, k_msm_small_combine_batch<F>>(ctx, 160 * 1024)));      // the whole 160 KiB of LDS for the two shells
     a.out = sums;
     a.planes = NB > 1 ? (uint32_t*)(ws + group * msm_batch_sums_bytes(sh)) : nullptr;
     const SmallBatchArgs av{a, {stride * 4, msm_batch_sums_bytes(sh) / 8, msm_batch_planes_bytes(sh) / 4}};
@@ -136,7 +105,7 @@ bool batch_shape(const kg_ctx* ctx, int curve, size_t n, MsmBatchShape* sh) {
 // outside the batched kernels' lengths: one blocking kg_commit per vector, the points and flags copied to the device behind them
 int batch_fallback(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n, size_t count, size_t stride,
                    uint64_t* d_out_xy, uint8_t* d_out_inf) {
-  const size_t pw = 2 * msm_batch_e64(curve);
+  const size_t pw = affine_words64(curve);
   std::vector<uint64_t> xy(count * pw);
   std::vector<uint8_t> inf(count);
   for (size_t b = 0; b < count; ++b) KG_TRY(kg_commit(ctx, curve, d_bases, d_inf, d_scalars + b * stride * 4, n, xy.data() + b * pw, inf.data() + b));
@@ -154,7 +123,7 @@ extern "C" {
 int kg_commit_batch_plan(int curve, size_t n, size_t count, size_t* per_launch) {
   if (per_launch) *per_launch = 0;
   MsmBatchShape sh;
-  if (!msm_batch_curve_ok(curve) || count == 0 || !batch_shape(nullptr, curve, n, &sh)) return 0;
+  if (!curve_ok(curve) || count == 0 || !batch_shape(nullptr, curve, n, &sh)) return 0;
   const size_t per = msm_batch_per_launch(msm_batch_vector_bytes(sh)), g = msm_batch_groups(per, count);
   if (per_launch) *per_launch = per;
   return g > (size_t)INT_MAX ? INT_MAX : (int)g;
@@ -170,18 +139,8 @@ int kg_commit_batch(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8
   KG_HIP(ctx, hipSetDevice(ctx->device));
   const size_t vb = msm_batch_vector_bytes(sh), per = msm_batch_per_launch(vb), groups = msm_batch_groups(per, count);
   KG_TRY(ctx->ws_small_batch.ensure(DevMem{ctx, "batched short-input scratch"}, msm_batch_scratch_bytes(vb, count)));
-  const int W = msm_batch_windows(sh);
-  SmallArgs a;
-  a.bases = d_bases; a.inf = d_inf; a.scalars = d_scalars; a.nr = (uint32_t)n; a.n = (uint32_t)(sh.glv ? 2 * n : n); a.glv = sh.glv ? 1 : 0; a.npl = sh.glv ? 4 : 8;
-  a.meta = nullptr; a.c = sh.c; a.W = W; a.r = sh.r; a.NB = msm_batch_ranges(sh);
-  uint32_t H[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (W > 0) small_bias(sh.c, W, H);
-  for (int j = 0; j < 8; ++j) a.H.w[j] = H[j];
-  a.out = nullptr; a.planes = nullptr; a.kt = nullptr; a.spill = nullptr; a.spill_cursor = nullptr;
-#ifdef KG_EXPERIMENTS
-  a.stamps = nullptr;
-#endif
-  const size_t pw = 2 * msm_batch_e64(curve);
+  SmallArgs a = small_args(d_bases, d_inf, d_scalars, n, sh.glv, sh.c, sh.r, msm_batch_windows(sh), msm_batch_ranges(sh));      // out, planes: per group (batch_group)
+  const size_t pw = affine_words64(curve);
   hipStream_t st = ctx->stream;
   for (size_t g = 0; g < groups; ++g) {                    // one after another on the stream: every group uses the same scratch
     const MsmBatchGroup grp = msm_batch_group(per, count, g);
@@ -189,9 +148,10 @@ int kg_commit_batch(kg_ctx* ctx, int curve, const uint64_t* d_bases, const uint8
     uint64_t* oxy = d_out_xy + grp.first * pw;
     uint8_t* oinf = d_out_inf + grp.first;
     char* ws = ctx->ws_small_batch.as<char>();
-    if (curve == KG_G1) KG_TRY((batch_group<Fq, FrParams>(ctx, st, a, sh, stride, grp.count, ws, oxy, oinf)));
-    else if (curve == KG_GRUMPKIN) KG_TRY((batch_group<Fr, FqParams>(ctx, st, a, sh, stride, grp.count, ws, oxy, oinf)));
-    else KG_TRY((batch_group<Fq2, FrParams>(ctx, st, a, sh, stride, grp.count, ws, oxy, oinf)));
+    KG_TRY(with_curve(curve, [&](auto cfg) {
+      using D = CurveDev<decltype(cfg)>;
+      return batch_group<typename D::F, typename D::SP>(ctx, st, a, sh, stride, grp.count, ws, oxy, oinf);
+    }));
   }
   return KG_OK;
   });

@@ -62,6 +62,19 @@ struct SmallArgs {
   uint64_t* stamps;           // KG_SMALL_STAMPS=1 (A/B builds): wall-clock ticks (10 ns) of workgroup (0, 0) at its phase boundaries
 #endif
 };
+// What the single call (msm_small.hip) and the batched one (msm_small_batch.hip) fill alike: the inputs, the shape (W windows of NB
+// workgroups; W == 0: empty vectors) and the digit bias.  Where the sums and planes go and the KT form's buffers are the caller's to set.
+inline SmallArgs small_args(const uint64_t* d_bases, const uint8_t* d_inf, const uint64_t* d_scalars, size_t n, bool glv, int c, int r, int W, int NB) {
+  SmallArgs a;
+  a.bases = d_bases; a.inf = d_inf; a.scalars = d_scalars; a.nr = (uint32_t)n; a.n = (uint32_t)(glv ? 2 * n : n); a.glv = glv ? 1 : 0; a.npl = glv ? 4 : 8;
+  a.meta = nullptr; a.c = c; a.W = W; a.r = r; a.NB = NB;
+  small_bias(c, W, a.H.w);
+  a.out = nullptr; a.planes = nullptr; a.kt = nullptr; a.spill = nullptr; a.spill_cursor = nullptr;
+#ifdef KG_EXPERIMENTS
+  a.stamps = nullptr;
+#endif
+  return a;
+}
 #ifdef KG_EXPERIMENTS
 #define KG_SM_STAMP(k) do { if (a.stamps && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.stamps[k] = wall_clock64(); } while (0)
 #else
@@ -97,20 +110,14 @@ template <class G> struct SmIO<Fp2<G>> {
     return {{from_ref<P>(r.w), from_ref<P>(r.w + 8)}, {from_ref<P>(r.w + 16), from_ref<P>(r.w + 24)}};
   }
 };
+static_assert(SmIO<G1Cfg::F>::E64 == coord_words64(G1Cfg::ID) && SmIO<GkCfg::F>::E64 == coord_words64(GkCfg::ID) &&
+              SmIO<G2Cfg::F>::E64 == coord_words64(G2Cfg::ID), "msm_small_kernels.h: a coordinate's words are curve_layout.h's");
 
 // raw internal XYZZ -> ABI words (x | y | zz | zzz)
-template <class P>
-__device__ __forceinline__ void sm_export_el(const Fp<P>& a, uint64_t* dst) {
-  uint32_t w[8];
-  to_ref(a, w);
-  store_words(dst, 0, w);
-}
-template <class G>
-__device__ __forceinline__ void sm_export_el(const Fp2<G>& a, uint64_t* dst) { sm_export_el(a.c0, dst); sm_export_el(a.c1, dst + 4); }
 template <class F>
 __device__ __forceinline__ void sm_export(const XYZZ<F>& p, uint64_t* dst) {
   constexpr int E = SmIO<F>::E64;
-  sm_export_el(p.x, dst); sm_export_el(p.y, dst + E); sm_export_el(p.zz, dst + 2 * E); sm_export_el(p.zzz, dst + 3 * E);
+  RefIO<F>::store(p.x, dst); RefIO<F>::store(p.y, dst + E); RefIO<F>::store(p.zz, dst + 2 * E); RefIO<F>::store(p.zzz, dst + 3 * E);
 }
 
 constexpr uint32_t SM_LIST_CAP = 4096;   // KT form: list entries a workgroup holds in LDS (more -- a skewed input -- spill to global memory)

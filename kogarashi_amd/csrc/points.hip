@@ -8,7 +8,7 @@
 //                              on XYZZ<Fq2>, the register footprint of k_acc_tasks<Fq2>).
 // Both write the status byte and fold the summary in the same launch: per 64-lane workgroup one ballot, one 64-bit atomicAdd of the popcount
 // and one 64-bit atomicMin of the lowest bad index, into two words of the context that k_summary_init (common.h) sets to (0, n) on the stream first.
-#include "common.h"
+#include "msm_common.h"
 #include "points_check.h"
 
 using namespace kg;
@@ -64,10 +64,11 @@ int run_check(kg_ctx* c, int curve, const uint64_t* d_xy, const uint8_t* d_inf, 
   unsigned long long* summary = c->ws_points.as<unsigned long long>();
   hipLaunchKernelGGL(k_summary_init<unsigned long long>, dim3(1), dim3(1), 0, c->stream, summary, (unsigned long long)n);
   const bool sub = (checks & KG_CHECK_SUBGROUP) != 0;
-  if (curve == KG_G1) launch_check<Fq, false>(c, d_xy, d_inf, n, d_status, summary);
-  else if (curve == KG_GRUMPKIN) launch_check<Fr, false>(c, d_xy, d_inf, n, d_status, summary);
-  else if (sub) launch_check<Fq2, true>(c, d_xy, d_inf, n, d_status, summary);
-  else launch_check<Fq2, false>(c, d_xy, d_inf, n, d_status, summary);
+  with_curve(curve, [&](auto cfg) {                            // the order-r test exists for the twist alone (G1, Grumpkin: cofactor 1)
+    using F = typename CurveDev<decltype(cfg)>::F;
+    if constexpr (decltype(cfg)::ID == KG_G2) { if (sub) return launch_check<F, true>(c, d_xy, d_inf, n, d_status, summary); }
+    launch_check<F, false>(c, d_xy, d_inf, n, d_status, summary);
+  });
   KG_HIP(c, hipGetLastError());
   return summary_read(c, summary, out_bad, out_first_bad);
 }
@@ -80,7 +81,7 @@ extern "C" {
 
 int kg_points_check(kg_ctx* c, int curve, const uint64_t* d_xy, const uint8_t* d_inf, size_t n, int checks, uint8_t* d_status, size_t* out_bad,
                     size_t* out_first_bad) {
-  if (!c || (curve != KG_G1 && curve != KG_GRUMPKIN && curve != KG_G2) || !checks_ok(checks)) return KG_ERR_BAD_ARG;
+  if (!c || !curve_ok(curve) || !checks_ok(checks)) return KG_ERR_BAD_ARG;
   if (n > 0 && !d_xy) return KG_ERR_BAD_ARG;
   KG_HIP(c, hipSetDevice(c->device));
   return run_check(c, curve, d_xy, d_inf, n, checks, d_status, out_bad, out_first_bad);

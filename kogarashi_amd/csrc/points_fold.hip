@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(G16_NT) k_points_muladd(const uint64_t* p_xy, 
     ops.put(2, add_xyzz(p, q));
   }
   const XYZZ<F> acc = muladd_chain_ops<F, SP>(ops, kw);
-  g16_put_affine<F, 4>(acc, out_xy + j * 8, out_inf + j);
+  put_affine_abi(acc, out_xy + j * 8, out_inf + j);
 }
 
 }  // namespace

@@ -25,8 +25,6 @@ void shard_range(size_t n, int rank, int world, size_t* lo, size_t* hi) {
   *hi = *lo + base + (r < extra ? 1 : 0);
 }
 
-int words_of(int curve) { return curve == KG_G2 ? 16 : 8; }
-
 // runs fn(i) for every context at once -- context 0 on the calling thread, the others on worker threads of context 0's pool; returns the
 // first failing status
 template <class Fn>
@@ -49,7 +47,7 @@ int for_each_ctx(kg_ctx* const* ctxs, int n_ctx, Fn fn) {
 
 // partial (x, y, z in {0, 1}) triples -> one affine sum
 int combine(kg_ctx* ctx0, int curve, const std::vector<uint64_t>& xyz, int n_ctx, uint64_t* out_xy, uint8_t* out_inf) {
-  const int E2 = words_of(curve), E = E2 / 2;
+  const int E2 = (int)affine_words64(curve), E = (int)coord_words64(curve);
   std::vector<uint64_t> pts((size_t)n_ctx * E2);
   std::vector<uint8_t> inf((size_t)n_ctx);
   for (int i = 0; i < n_ctx; ++i) {
@@ -84,10 +82,10 @@ int kg_shard_range(size_t n, int rank, int world, size_t* lo, size_t* hi) {
 int kg_commit_sharded(kg_ctx* const* ctxs, int n_ctx, int curve, const uint64_t* const* d_bases, const uint8_t* const* d_inf,
                       const uint64_t* const* d_scalars, const size_t* n_local, uint64_t* out_xy, uint8_t* out_inf) {
   return kg::kg_guarded((ctxs && n_ctx > 0 ? ctxs[0] : nullptr), [&]() -> int {
-  if (!ctxs || n_ctx < 1 || n_ctx > 64 || curve < 0 || curve > KG_G2 || !d_bases || !d_scalars || !n_local || !out_xy || !out_inf) return KG_ERR_BAD_ARG;
+  if (!ctxs || n_ctx < 1 || n_ctx > 64 || !curve_ok(curve) || !d_bases || !d_scalars || !n_local || !out_xy || !out_inf) return KG_ERR_BAD_ARG;
   for (int i = 0; i < n_ctx; ++i)
     if (!ctxs[i] || (n_local[i] && (!d_bases[i] || !d_scalars[i]))) return KG_ERR_BAD_ARG;
-  const int E = words_of(curve) / 2;
+  const int E = (int)coord_words64(curve);
   std::vector<uint64_t> xyz((size_t)n_ctx * 3 * E);
   const int rc = for_each_ctx(ctxs, n_ctx, [&](int i) {
     return kg_msm(ctxs[i], curve, d_bases[i], d_inf ? d_inf[i] : nullptr, d_scalars[i], n_local[i], xyz.data() + (size_t)i * 3 * E);
@@ -100,12 +98,12 @@ int kg_commit_sharded(kg_ctx* const* ctxs, int n_ctx, int curve, const uint64_t*
 int kg_msm_sharded(kg_ctx* const* ctxs, int n_ctx, int curve, const uint64_t* const* d_bases, const uint8_t* const* d_inf,
                    const uint64_t* const* d_scalars, const size_t* n_local, uint64_t* out_xyz) {
   return kg::kg_guarded((ctxs && n_ctx > 0 ? ctxs[0] : nullptr), [&]() -> int {
-  if (!out_xyz || curve < 0 || curve > KG_G2) return KG_ERR_BAD_ARG;
+  if (!out_xyz || !curve_ok(curve)) return KG_ERR_BAD_ARG;
   uint64_t xy[16];
   uint8_t inf = 0;
   KG_TRY(kg_commit_sharded(ctxs, n_ctx, curve, d_bases, d_inf, d_scalars, n_local, xy, &inf));
   if (inf) { msm_identity(curve, out_xyz); return KG_OK; }
-  const int E = words_of(curve) / 2;
+  const int E = (int)coord_words64(curve);
   uint64_t one[24];
   msm_identity(curve, one);                        // (0, 1, 0): its y is the field's one in the ABI form
   for (int k = 0; k < 2 * E; ++k) out_xyz[k] = xy[k];
@@ -119,7 +117,7 @@ int kg_sharded_key_create(kg_ctx* const* ctxs, int n_ctx, int curve, const uint6
   return kg::kg_guarded((ctxs && n_ctx > 0 ? ctxs[0] : nullptr), [&]() -> int {
   if (!out) return KG_ERR_BAD_ARG;
   *out = nullptr;
-  if (!ctxs || n_ctx < 1 || n_ctx > 64 || curve < 0 || curve > KG_G2 || (n && !h_bases)) return KG_ERR_BAD_ARG;
+  if (!ctxs || n_ctx < 1 || n_ctx > 64 || !curve_ok(curve) || (n && !h_bases)) return KG_ERR_BAD_ARG;
   for (int i = 0; i < n_ctx; ++i)
     if (!ctxs[i]) return KG_ERR_BAD_ARG;
   kg_sharded_key* K = new kg_sharded_key();
@@ -127,7 +125,7 @@ int kg_sharded_key_create(kg_ctx* const* ctxs, int n_ctx, int curve, const uint6
   K->curve = curve; K->n = n;
   K->lo.resize((size_t)n_ctx); K->hi.resize((size_t)n_ctx);
   K->d_bases.assign((size_t)n_ctx, nullptr); K->d_inf.assign((size_t)n_ctx, nullptr);
-  const size_t wb = (size_t)words_of(curve) * 8;
+  const size_t wb = affine_words64(curve) * 8;
   const int rc = for_each_ctx(ctxs, n_ctx, [&](int i) {
     size_t lo, hi;
     shard_range(n, i, n_ctx, &lo, &hi);
@@ -166,7 +164,7 @@ int kg_sharded_key_commit(kg_sharded_key* K, const uint64_t* h_scalars, size_t n
   if (!K || !out_xy || !out_inf || (n && !h_scalars)) return KG_ERR_BAD_ARG;
   if (n > K->n) n = K->n;                              // zip semantics of commit (pedersen.rs:16-17)
   const int n_ctx = (int)K->ctxs.size();
-  const int E = words_of(K->curve) / 2;
+  const int E = (int)coord_words64(K->curve);
   std::vector<uint64_t> xyz((size_t)n_ctx * 3 * E);
   const int rc = for_each_ctx(K->ctxs.data(), n_ctx, [&](int i) {
     const size_t lo = K->lo[(size_t)i] < n ? K->lo[(size_t)i] : n, hi = K->hi[(size_t)i] < n ? K->hi[(size_t)i] : n;

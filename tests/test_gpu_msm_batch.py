@@ -160,6 +160,14 @@ def test_vectors_of_different_kinds_in_one_batch(ctx, oracle, pyoracle):
     run_batch(ctx, 0, db.ptr, di.ptr, ds.ptr, n, 0, n)
 
 
+@pytest.mark.parametrize("curve", [0, 1, 2])
+def test_empty_vectors_are_identities_on_every_curve(ctx, oracle, curve):
+    """n = 0 reads neither bases nor scalars: the finish kernel alone runs and writes (0, 1) with flag 1 for every vector -- the identity
+    branch of the affine writer every kernel shares (common.h put_affine_abi), once per coordinate field"""
+    xy, fl = run_batch(ctx, curve, 0, 0, 0, 0, 3, 0)
+    assert (fl == 1).all() and (xy == identity_words(oracle, curve)).all()
+
+
 @pytest.mark.parametrize("c,r", [(2, 0), (3, 2), (5, 1), (6, 0), (8, 3)])
 def test_forced_shapes(ctx, oracle, c, r):
     """kg_msm_set_small applies to the batch as it does to kg_commit: window widths that do not divide the halves' 128 bits, one bucket per
